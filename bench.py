@@ -1,11 +1,23 @@
 """Benchmark: device-resident batched CRC32C (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, ms_per_step, pct_hbm_peak, config). `--full` adds everything
+else described below to the same line: the parity check against the oracle,
+`roofline` (with `ceiling` and `traffic`), `split` and `cpu_baseline`.
+`--dump-outputs DIR` writes the CRCs of the last timed step (what a caller of
+the engine would read from its output buffer) as DIR/crc32c.npy (float64, one
+value per block; crc32c_rank<r>.npy at N > 1). The blocks are seeded, the
+window each timed step reads depends only on the arguments, and the last
+step writes a buffer no other step in flight writes (EngineRunner.step_last),
+so two builds can be compared CRC for CRC.
 
 Configs (BASELINE.json "configs"; the default line is the headline):
   headline        10,000 x 4 KiB blocks per GPU per step (the metric's
-                  workload); the line also carries `split`, config 5 measured
-                  in the same run.
+                  workload); with --full the line also carries `split`,
+                  config 5 measured in the same run.
   blocks1m_split  config 5: ONE batch of 1M x 4 KiB blocks split across the
                   ranks (shard.shard_range), aggregate GiB/s.
   blocks1m        config 4: 1M x 4 KiB blocks per GPU per step.
@@ -25,11 +37,13 @@ process, before any GPU call). Config 5 below 1 GiB per slice keeps several
 copies of the slice per rank and rotates over them (MALL-cold every step).
 
 Timed region (every config, every rank; `timed_region`): time-based warm-up
-(>= --warmup-ms and >= W steps), barrier, synchronize, t0, K steps, engine
-wait, synchronize, t1, barrier; elapsed = max over ranks of t1 - t0 (common
-start to last completion). value = all ranks' bytes / elapsed.
+(>= --warmup-ms and >= W steps; steps beyond W come in whole rotations, so
+the windows the timed steps read do not depend on the clock), barrier,
+synchronize, t0, K steps, engine wait, synchronize, t1, barrier; elapsed =
+max over ranks of t1 - t0 (common start to last completion). value = all
+ranks' bytes / elapsed; ms_per_step = elapsed / K.
 
-roofline: algorithmic bytes per launch (nblocks x (block + 4 B CRC out),
+roofline (--full): algorithmic bytes per launch (nblocks x (block + 4 B CRC out),
 SURVEY.md §8(d)) / the launch's duration, from the packet processor's
 start/end timestamps of each dispatch (HSA profiling, the engine's HIP-event
 counterpart): `achieved` prices a launch running alone (ordered dispatches,
@@ -37,7 +51,7 @@ the same kernel a rocprofv3 kernel trace of `--isolated` times); `pipelined`
 prices the device span of K overlapped launches / K. `traffic`: HBM-side
 bytes per isolated launch from a rocprofv3 FETCH_SIZE pass over this run's
 own code (a child profiler process, N = 1 headline only; --no-pmc skips it).
-cpu_baseline: the reference's util/crc32c.cc (compiled in place into
+cpu_baseline (--full): the reference's util/crc32c.cc (compiled in place into
 oracle/_ref) on this host.
 """
 from __future__ import annotations
@@ -145,11 +159,17 @@ def timed_region(runner, comm: Comm, steps: int, warmup: int, warmup_s: float,
     from a common start (barrier + sync) to this rank's last completion
     (finish + sync); returns (max over ranks in seconds, next step index).
     `runner` has step(i), finish() and sync(). Step indices continue from `first` so the
-    timed steps read windows the warm-up did not just leave in the cache."""
+    timed steps read windows the warm-up did not just leave in the cache.
+    Warm-up steps beyond `warmup` come in whole rotations (runner.nrot), so
+    timed step k reads window (first + warmup + k) % nrot whatever the clock
+    did: the same arguments give the same inputs to every timed step. A
+    runner with step_last(i) gets the last timed step through it (the step
+    whose output --dump-outputs writes)."""
     i = first
     t_end = time.perf_counter() + warmup_s
     n = 0
-    while n < warmup or time.perf_counter() < t_end:
+    nrot = getattr(runner, "nrot", 1)
+    while n < warmup or time.perf_counter() < t_end or (n - warmup) % nrot:
         runner.step(i)
         i += 1
         n += 1
@@ -161,8 +181,11 @@ def timed_region(runner, comm: Comm, steps: int, warmup: int, warmup_s: float,
     runner.sync()
     t0 = time.perf_counter()
     fw = getattr(runner, "final_window", 0)
+    step_last = getattr(runner, "step_last", None)
     for k in range(steps):
-        if k >= steps - fw:
+        if k == steps - 1 and step_last is not None:
+            step_last(i + k)
+        elif k >= steps - fw:
             runner.step(i + k, final=True)
         else:
             runner.step(i + k)
@@ -218,9 +241,20 @@ class EngineRunner:
         self.outs_t = outs
         self.nrot = nrot
         self.flags = 0
+        # The last timed step's own output buffer. Steps on different queues
+        # are not ordered against each other, so a buffer of the ring may
+        # still be written by the step len(outs) before: the ring is fine for
+        # timing, and this one holds exactly what the last step computed.
+        self.last_out_t = torch.empty_like(outs[0])
+        self.last_out = self.last_out_t.data_ptr()
         # the engine does not follow HIP streams: the kernels that wrote the
         # blocks (torch.randint) must be complete before the first submit
         torch.cuda.synchronize()
+        # one submit per window into last_out, so the last step's arguments
+        # are in the engine's kernarg cache like every other step's
+        for w in range(nrot):
+            self.step_last(w)
+        eng.wait()
 
     # the last submits before a wait, one per queue, carry LVKV_FLAG_FINAL
     # (their completion releases the results, so the wait needs no barrier
@@ -234,11 +268,24 @@ class EngineRunner:
         if rc != 0:
             raise SystemExit(f"bench: lvkv_engine_crc32c_uniform failed ({rc})")
 
+    def step_last(self, i):
+        """The last step before a wait (timed_region): as step(i, final=True),
+        into last_out."""
+        rc = self.submit(self.h, self.bases[i % self.nrot], self.stride, self.L, 0,
+                         self.last_out, self.nb, self.flags | 8)  # LVKV_FLAG_FINAL
+        if rc != 0:
+            raise SystemExit(f"bench: lvkv_engine_crc32c_uniform failed ({rc})")
+
     def finish(self):
         self.eng.wait()
 
     def sync(self):
         self.torch.cuda.synchronize()
+
+    def last_output(self):
+        """The CRCs the last timed step wrote (one per block), as the caller
+        reads them."""
+        return self.last_out_t[:self.nb]
 
 
 def make_buffers(torch, dev, rank, nb, stride, rotate_bytes, extra=64):
@@ -248,6 +295,20 @@ def make_buffers(torch, dev, rank, nb, stride, rotate_bytes, extra=64):
     buf = torch.randint(0, 256, (nrot * window + extra,), dtype=torch.uint8, device=dev,
                         generator=gen)
     return buf, nrot, window
+
+
+def dump_outputs(out_dir, runner, rank, world):
+    """--dump-outputs: the CRCs of the last timed step, every block's, as
+    float64 (exact for 32-bit values): 10k blocks are 80 KB, 1M blocks 8 MB.
+    All ranks together stay under 64 MB: beyond that share a rank writes a
+    fixed, seeded sample of its blocks (in block order)."""
+    crc = runner.last_output().cpu().numpy().view(np.uint32).astype(np.float64)
+    limit = 60_000_000 // world // 8
+    if crc.size > limit:
+        crc = crc[np.sort(np.random.default_rng(0x1EDC6F41).choice(crc.size, limit, replace=False))]
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / ("crc32c.npy" if world == 1 else f"crc32c_rank{rank}.npy"), crc)
 
 
 def parity_check(buf, outs0, nb, L, stride, crc_off, rank, what, chunk=1 << 18):
@@ -394,8 +455,16 @@ def main():
                     help="warm-up lasts at least this long, whatever --warmup says")
     ap.add_argument("--config", default="headline", choices=sorted(CONFIGS))
     ap.add_argument("--rotate-bytes", type=float, default=1.25 * GIB)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-split", action="store_true", help="skip config 5 in the headline line")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the first batch against the oracle and measure the "
+                         "roofline (ceiling, traffic), config 5 (`split`) and the CPU "
+                         "baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's CRCs as DIR/crc32c.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-split", action="store_true",
+                    help="with --full: skip config 5 in the headline line")
     ap.add_argument("--no-pmc", action="store_true",
                     help="skip the rocprofv3 FETCH_SIZE pass behind roofline.traffic")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
@@ -430,6 +499,9 @@ def main():
     lvkv = g.load_package()
 
     if args.plumbing_cpu:
+        if args.dump_outputs:
+            raise SystemExit("bench: --dump-outputs writes the engine's output; "
+                             "--plumbing-cpu has none")
         _plumbing_cpu(args, lvkv, world, rank, warm_s)
         return
 
@@ -445,6 +517,8 @@ def main():
         runner, rec = split_measure(
             lambda s, c: _split_runner(torch, lvkv, eng, dev, rank, s, c), comm, rank, world,
             args.steps, args.warmup, warm_s, total=args.split_total)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, runner, rank, world)
         if rank == 0:
             line = _line_base(args, world, rec["value"], rec["ms_per_step"] / 1e3,
                               {"workload": rec["workload"], "total_blocks": args.split_total,
@@ -466,7 +540,8 @@ def main():
     runner.step(0)
     runner.finish()
     runner.sync()
-    checked = parity_check(buf, outs[0], nb, L, stride, crc_off, rank, args.config)
+    checked = (parity_check(buf, outs[0], nb, L, stride, crc_off, rank, args.config)
+               if args.full else 0)
 
     if args.isolated:
         runner.flags = 2
@@ -479,9 +554,22 @@ def main():
         return
 
     elapsed, nxt = timed_region(runner, comm, args.steps, args.warmup, warm_s, first=1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner, rank, world)
     ms_per_step = elapsed / args.steps * 1e3
     value = world * nb * L * args.steps / elapsed / GIB
     algo_bytes = nb * (L + 4)
+    config = {"workload": desc, "nblocks_per_gpu": nb, "block_bytes": L, "stride": stride,
+              "rotation_buffers": nrot, "rotation_bytes": nrot * window,
+              "path": "AQL engine, batches overlapped" + ("" if burst else ", general walk"),
+              "parallelism": f"{world} independent block batches (no collective)"}
+    if not args.full:
+        if rank == 0:
+            line = _line_base(args, world, value, ms_per_step / 1e3, config)
+            line["pct_hbm_peak"] = round(100.0 * value * GIB / 1e9 / HBM_PEAK_GBS / world, 2)
+            print(json.dumps(line), flush=True)
+        _end(world)
+        return
 
     # every rank prices its own launches (its own GPU's packet-processor times)
     roof = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -547,12 +635,8 @@ def main():
             roof["traffic_source"] = t["source"] + (f"; rank 0 of {world}" if world > 1 else "")
 
     if rank == 0:
-        line = _line_base(args, world, value, ms_per_step / 1e3, {
-            "workload": desc, "nblocks_per_gpu": nb, "block_bytes": L, "stride": stride,
-            "rotation_buffers": nrot, "rotation_bytes": nrot * window,
-            "path": "AQL engine, batches overlapped" + ("" if burst else ", general walk"),
-            "parallelism": f"{world} independent block batches (no collective)",
-            "parity_blocks": sum(r["parity_blocks"] for r in ranks)})
+        config["parity_blocks"] = sum(r["parity_blocks"] for r in ranks)
+        line = _line_base(args, world, value, ms_per_step / 1e3, config)
         line["pct_hbm_peak"] = round(100.0 * value * GIB / 1e9 / HBM_PEAK_GBS / world, 2)
         line["roofline"] = roof
         if world > 1:
@@ -768,7 +852,8 @@ def _plumbing_cpu(args, lvkv, world, rank, warm_s):
         line["split"] = rec
         line["rank_counts"] = [r["nblocks"] for r in ranks]
         line["roofline"] = {"per_rank": ranks}
-        line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(args.cpu_seconds)
+        if args.full:
+            line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(args.cpu_seconds)
         line["data"] = "plumbing-cpu: NOT a device measurement"
         print(json.dumps(line), flush=True)
     _end(world)

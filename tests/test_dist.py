@@ -149,7 +149,7 @@ def test_bench_gpus2_launches_two_ranks():
     both: n_gpus, the split's ranks and each rank's slice."""
     rc, line, err = _bench(["--gpus", "2", "--plumbing-cpu", "--config", "blocks1m_split",
                             "--split-total", "65", "--steps", "3", "--warmup", "1",
-                            "--warmup-ms", "0", "--cpu-seconds", "0.3"])
+                            "--warmup-ms", "0", "--cpu-seconds", "0.3", "--full"])
     assert rc == 0, err[-2000:]
     assert line["n_gpus"] == 2
     assert line["split"]["ranks"] == 2 and line["split"]["total_blocks"] == 65
@@ -179,3 +179,66 @@ def test_bench_refuses_world_mismatch():
                            env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert rc != 0 and line is None
     assert "--gpus 2" in err
+
+
+class _RecordingRunner:
+    """bench.EngineRunner's interface with nothing behind it: records the
+    step indices; `nrot` windows, `nb` CRCs a step; the last timed step
+    writes its own buffer (step_last / last_output)."""
+
+    def __init__(self, nrot, nb=6):
+        self.nrot, self.nb = nrot, nb
+        self.steps, self.last_steps = [], []
+        self.last_out_t = torch.zeros(nb + 2, dtype=torch.int32)
+
+    def step(self, i, final=False):
+        self.steps.append(i)
+
+    def step_last(self, i):
+        self.steps.append(i)
+        self.last_steps.append(i)
+        # a CRC-like 32-bit pattern of (window, block), high bit set
+        self.last_out_t[:self.nb] = torch.tensor(
+            [(0x80000000 | ((i % self.nrot) << 8) | b) - (1 << 32) for b in range(self.nb)],
+            dtype=torch.int32)
+
+    def finish(self):
+        pass
+
+    def sync(self):
+        pass
+
+    def last_output(self):
+        import bench
+        return bench.EngineRunner.last_output(self)
+
+
+@pytest.mark.parametrize("nrot,warmup,warmup_s", [(33, 5, 0.02), (33, 40, 0.0), (1, 2, 0.01),
+                                                   (7, 0, 0.015)])
+def test_timed_steps_read_the_same_windows_whatever_the_clock(nrot, warmup, warmup_s):
+    """The time-based part of the warm-up runs whole rotations, so timed step
+    k reads window (first + warmup + k) % nrot in every run (--dump-outputs
+    compares two builds on the last step's output), and exactly `steps` steps
+    are timed."""
+    import bench
+    r = _RecordingRunner(nrot)
+    steps, first = 9, 1
+    _, nxt = bench.timed_region(r, bench.Comm(1), steps, warmup, warmup_s, first=first)
+    assert r.steps == list(range(first, nxt)) and r.last_steps == [nxt - 1]
+    n_warm = len(r.steps) - steps
+    assert n_warm >= warmup and (n_warm - warmup) % nrot == 0
+    assert [i % nrot for i in r.steps[-steps:]] == [(first + warmup + k) % nrot
+                                                    for k in range(steps)]
+
+
+def test_dump_outputs_writes_the_last_steps_crcs(tmp_path):
+    """--dump-outputs: DIR/crc32c.npy holds the last timed step's CRCs, one per
+    block, as unsigned 32-bit values in float64 (exact)."""
+    import bench
+    r = _RecordingRunner(5)
+    _, nxt = bench.timed_region(r, bench.Comm(1), 3, 2, 0.0, first=1)
+    bench.dump_outputs(tmp_path / "out", r, 0, 1)
+    got = np.load(tmp_path / "out" / "crc32c.npy")
+    assert got.dtype == np.float64 and got.shape == (r.nb,)
+    w = (nxt - 1) % 5
+    assert got.tolist() == [float(0x80000000 | (w << 8) | b) for b in range(r.nb)]

@@ -295,6 +295,27 @@ def test_bench_parity_check_catches_a_wrong_block(lvkv, oracle, gpu):
         bench.parity_check(buf, out, nb, L, L, 0, 0, "test", chunk=8192)
 
 
+def test_bench_last_timed_step_output(lvkv, oracle, eng, gpu):
+    """What `bench.py --dump-outputs` writes: after bench.timed_region over
+    bench.EngineRunner (5 windows, 4 ring buffers, overlapped steps), the
+    runner's last_output() is the CRC of every block of the window the last
+    timed step read, (first + warmup + steps - 1) % nrot, whatever the
+    warm-up's clock did."""
+    import torch
+
+    import bench
+    nb, L, steps, warmup, first = 2000, 4096, 50, 3, 1
+    buf, nrot, window = bench.make_buffers(torch, gpu, 0, nb, L, 5 * nb * L)
+    assert nrot == 5
+    outs = [torch.empty(nb, dtype=torch.int32, device=gpu) for _ in range(4)]
+    r = bench.EngineRunner(lvkv, eng, buf, nb, L, L, 0, nrot, window, outs)
+    _, nxt = bench.timed_region(r, bench.Comm(1), steps, warmup, 0.002, first=first)
+    assert (nxt - first - steps - warmup) % nrot == 0
+    w = (first + warmup + steps - 1) % nrot
+    want = oracle.uniform(buf[w * window:(w + 1) * window].cpu().numpy(), nb, L, threads=8)
+    assert np.array_equal(r.last_output().cpu().numpy().view(np.uint32), want)
+
+
 @pytest.mark.parametrize("nq,finals", [(3, 3), (3, 1), (1, 1), (4, 2)])
 def test_engine_final_flag_fence(lvkv, oracle, eng, gpu, nq, finals):
     """LVKV_FLAG_FINAL on the last `finals` submits before a wait: queues

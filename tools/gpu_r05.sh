@@ -37,10 +37,10 @@ if want tests; then
   tail -1 $O/smoke.log
 fi
 if want bench; then
-  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err \
+  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_k20.json 2> $O/bench_k20.err \
     || { echo "bench failed"; tail -20 $O/bench_k20.err; exit 1; }
   cat $O/bench_k20.json
-  timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err \
+  timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err \
     || { echo "bench failed"; tail -20 $O/bench_default.err; exit 1; }
   cat $O/bench_default.json
 fi
@@ -57,7 +57,7 @@ fi
 if want edgesdev; then  # AQL rings in device memory (ROCr HSA_ALLOCATE_QUEUE_DEV_MEM)
   HSA_ALLOCATE_QUEUE_DEV_MEM=1 timeout -k 10 300 python tools/probe/edges.py --scopes=1,0,2 > $O/edgesdev.log 2>&1 || { tail -20 $O/edgesdev.log; exit 1; }
   grep -v amdgpu.ids $O/edgesdev.log | tail -12
-  HSA_ALLOCATE_QUEUE_DEV_MEM=1 timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > $O/bench_k20_devq.json 2> $O/bench_k20_devq.err || { tail -20 $O/bench_k20_devq.err; exit 1; }
+  HSA_ALLOCATE_QUEUE_DEV_MEM=1 timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-pmc --no-cpu-baseline > $O/bench_k20_devq.json 2> $O/bench_k20_devq.err || { tail -20 $O/bench_k20_devq.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench_k20_devq.json')); print('devq k20', d['pct_hbm_peak'], d['roofline']['kernel_us_avg'], d['roofline']['pipelined']['period_us'])"
 fi
 if want edges; then
