@@ -139,6 +139,45 @@ int lvkv_sst_write_blocks_level_device(const void* d_raw, const uint64_t* d_raw_
                                        uint32_t* d_handle_size, uint8_t* d_type, uint64_t* d_end,
                                        void* stream);
 
+/*
+ * The writer for blocks of any size, with the codec's verdict per block.
+ * Semantics of lvkv_sst_write_blocks_level_device, except:
+ *  - d_status[i] = the codec's status for block i: LVKV_ZSTD_OK, or
+ *    LVKV_ZSTD_TOO_LARGE for a block the device did not compress (written
+ *    raw, type 0 -- where TableBuilder::WriteBlock would have compressed it,
+ *    so the host has to redo that block if the image is to be the
+ *    reference's). With compression 0 every status is OK. A block the
+ *    12.5% rule kept raw has status OK.
+ *  - compression 1 (snappy): every block compresses whatever its length
+ *    (fragments are 64 KiB); max_len is not used.
+ *  - compression 2 (zstd): blocks up to min(max_len,
+ *    LVKV_ZSTD_COMPRESS_BIG_MAX_BLOCK) compress at levels <= 2 except 0;
+ *    longer blocks (frames of several Zstd blocks) are TOO_LARGE. Levels 0
+ *    and >= 3 are LVKV_ERR_INVALID.
+ *  - nblocks == 0 is handled before every other check: LVKV_OK with d_end[0]
+ *    = file_offset, whatever the compression and level.
+ *  - the scratch is ragged: block i's compressed form lives at an exclusive
+ *    scan (on the device) of max(snappy MaxCompressedLength,
+ *    ZSTD_compressBound)(d_raw_len[i]) rounded up to 16, so it grows with the
+ *    bytes written and not with nblocks x max_len.
+ *    lvkv_sst_write_scratch_bytes_v2(nblocks, total_raw_bytes, max_len) is
+ *    enough for any batch of nblocks blocks of total_raw_bytes in all (it
+ *    includes the zstd compressor's fixed pool for max_len, which does not
+ *    depend on the batch). scratch_bytes = the bytes at d_scratch; a block
+ *    whose slot would not fit (the caller's total was too small) is reported
+ *    TOO_LARGE and written raw, never past the scratch. A NULL d_scratch or
+ *    d_status, or a scratch too small for the fixed part, is
+ *    LVKV_ERR_INVALID.
+ */
+size_t lvkv_sst_write_scratch_bytes_v2(size_t nblocks, uint64_t total_raw_bytes, uint32_t max_len);
+int lvkv_sst_write_blocks_status_device(const void* d_raw, const uint64_t* d_raw_off,
+                                        const uint32_t* d_raw_len, size_t nblocks, int compression,
+                                        int zstd_level, uint32_t max_len, void* d_scratch,
+                                        void* d_file, uint64_t file_offset,
+                                        uint64_t* d_handle_off, uint32_t* d_handle_size,
+                                        uint8_t* d_type, uint64_t* d_end, size_t scratch_bytes,
+                                        uint8_t* d_status, void* stream);
+
 /* ReadBlock verdicts */
 #define LVKV_READ_OK 0
 #define LVKV_READ_CHECKSUM 1        /* "block checksum mismatch" (table/format.cc:95-98) */

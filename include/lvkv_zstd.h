@@ -9,11 +9,12 @@
  * blocks on `stream` (a hipStream_t, NULL = the default stream) and returns
  * once the work is enqueued.
  *
- * Bytes: libzstd 1.4.9's (the zstd this image carries, the library
- * port/port_stdcxx.h:133-199 would link). The compressor emits exactly the
- * frame port::Zstd_Compress gets from ZSTD_compress2 after
- * ZSTD_getCParams(level, max(n, 1), 0) + ZSTD_CCtx_setCParams; the
- * decompressor accepts exactly the frames ZSTD_decompressDCtx accepts and
+ * Bytes: identical to libzstd 1.4.9 driven as port::Zstd_Compress
+ * (port/port_stdcxx.h:133-161) -- and to that version only: another libzstd
+ * may choose other parameters or tie-breaks and write another, equally valid,
+ * frame. The compressor emits exactly the frame port::Zstd_Compress gets from
+ * 1.4.9's ZSTD_compress2 after ZSTD_getCParams(level, max(n, 1), 0) +
+ * ZSTD_CCtx_setCParams; the decompressor accepts exactly the frames ZSTD_decompressDCtx accepts and
  * produces the same bytes.
  */
 #ifndef LVKV_ZSTD_H_
@@ -63,6 +64,30 @@ int lvkv_zstd_compress_device(const void* d_src, const uint64_t* d_src_off,
                               const uint32_t* d_src_len, void* d_dst, const uint64_t* d_dst_off,
                               uint32_t* d_dst_len, uint8_t* d_status, size_t nblocks,
                               uint32_t max_len, int level, void* stream);
+
+/*
+ * The same call for blocks of any length up to
+ * LVKV_ZSTD_COMPRESS_BIG_MAX_BLOCK (ZSTD_BLOCKSIZE_MAX: one Zstd block a
+ * frame). Blocks up to LVKV_ZSTD_COMPRESS_MAX_BLOCK go through the kernel of
+ * lvkv_zstd_compress_device and get the same bytes; a second kernel on the
+ * same stream compresses the longer ones out of d_scratch. max_len may take
+ * any value: d_status[i] is LVKV_ZSTD_TOO_LARGE for a block longer than
+ * min(max_len, LVKV_ZSTD_COMPRESS_BIG_MAX_BLOCK) -- a frame of several Zstd
+ * blocks is the host library's -- and LVKV_ZSTD_UNSUPPORTED for the levels
+ * whose strategy is not ZSTD_fast (0 and >= 3). d_scratch:
+ * lvkv_zstd_compress_big_scratch_bytes(max_len) bytes, a fixed pool that does
+ * not grow with nblocks (0 bytes, and d_scratch may be NULL, for max_len <=
+ * LVKV_ZSTD_COMPRESS_MAX_BLOCK, when no block can need it); a NULL or
+ * smaller scratch is LVKV_ERR_INVALID. The scratch belongs to the call until
+ * the stream has run it: concurrent calls need a scratch each.
+ */
+#define LVKV_ZSTD_COMPRESS_BIG_MAX_BLOCK 131072u
+size_t lvkv_zstd_compress_big_scratch_bytes(uint32_t max_len);
+int lvkv_zstd_compress_big_device(const void* d_src, const uint64_t* d_src_off,
+                                  const uint32_t* d_src_len, void* d_dst,
+                                  const uint64_t* d_dst_off, uint32_t* d_dst_len,
+                                  uint8_t* d_status, size_t nblocks, uint32_t max_len, int level,
+                                  void* d_scratch, size_t scratch_bytes, void* stream);
 
 /*
  * port::Zstd_GetUncompressedLength (port/port_stdcxx.h:163-177) over a batch:

@@ -163,6 +163,16 @@ def _load() -> ctypes.CDLL:
     L.lvkv_zstd_compress_bound.restype = sz
     L.lvkv_zstd_compress_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, u32, i32, vp]
     L.lvkv_zstd_compress_device.restype = i32
+    L.lvkv_zstd_compress_big_scratch_bytes.argtypes = [u32]
+    L.lvkv_zstd_compress_big_scratch_bytes.restype = sz
+    L.lvkv_zstd_compress_big_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, u32, i32, vp, sz,
+                                                vp]
+    L.lvkv_zstd_compress_big_device.restype = i32
+    L.lvkv_sst_write_scratch_bytes_v2.argtypes = [sz, u64, u32]
+    L.lvkv_sst_write_scratch_bytes_v2.restype = sz
+    L.lvkv_sst_write_blocks_status_device.argtypes = [vp, vp, vp, sz, i32, i32, u32, vp, vp, u64,
+                                                      vp, vp, vp, vp, sz, vp, vp]
+    L.lvkv_sst_write_blocks_status_device.restype = i32
     L.lvkv_sst_read_blocks_device.argtypes = [vp, vp, vp, sz, i32, vp, vp, vp, vp, vp, u32, vp]
     L.lvkv_sst_read_blocks_device.restype = i32
     L.lvkv_strerror.argtypes = [i32]
@@ -657,6 +667,64 @@ def zstd_compress(src, offsets, lengths, *, level: int = 1, max_len: Optional[in
     return dst, dst_offsets, out_len, status
 
 
+ZSTD_COMPRESS_BIG_MAX_BLOCK = 131072
+
+
+def zstd_compress_big_scratch_bytes(max_len: int) -> int:
+    """The scratch zstd_compress_big's second kernel works in: a fixed pool,
+    the same for every batch (0 for max_len <= ZSTD_COMPRESS_MAX_BLOCK)."""
+    return int(_lib.lvkv_zstd_compress_big_scratch_bytes(max(0, min(int(max_len), 0xFFFFFFFF))))
+
+
+def zstd_compress_big(src, offsets, lengths, *, level: int = 1, max_len: Optional[int] = None,
+                      dst=None, dst_offsets=None, scratch=None, stream=None):
+    """zstd_compress for blocks of any length up to ZSTD_COMPRESS_BIG_MAX_BLOCK
+    (one Zstd block a frame): identical to libzstd 1.4.9 driven as
+    port::Zstd_Compress. Blocks up to ZSTD_COMPRESS_MAX_BLOCK take the kernel
+    of zstd_compress (the same bytes); the longer ones a second kernel on the
+    same stream. max_len may be anything: a block longer than min(max_len,
+    ZSTD_COMPRESS_BIG_MAX_BLOCK) is ZSTD_TOO_LARGE (the host library's), a
+    level that is not ZSTD_fast (0, >= 3) ZSTD_UNSUPPORTED. The scratch is
+    allocated here unless given (zstd_compress_big_scratch_bytes(max_len)
+    bytes; it belongs to the call until the stream has run it). Returns the
+    same 4-tuple as zstd_compress."""
+    torch = _torch()
+    n = offsets.numel()
+    dev = src.device
+    if lengths.numel() != n:
+        raise ValueError("offsets and lengths differ in length")
+    if max_len is None:
+        max_len = int(lengths.max().item()) if n else 0
+    max_len = max(0, min(int(max_len), 0xFFFFFFFF))
+    if dst is None:
+        lens = lengths.to(torch.int64)
+        room = lens + (lens >> 8) + torch.clamp((131072 - lens) >> 11, min=0)
+        dst_offsets = _packed_offsets(torch, room, dev)
+        dst = torch.empty(max(1, int(room.sum().item())) if n else 1, dtype=torch.uint8,
+                          device=dev)
+    elif dst_offsets is None:
+        raise ValueError("dst needs dst_offsets")
+    out_len = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n:
+        need = zstd_compress_big_scratch_bytes(max_len)
+        if scratch is None and need:
+            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lvkv_zstd_compress_big_device(
+                _dev_ptr(src, "src", (torch.uint8, torch.int8)),
+                _dev_ptr(offsets, "offsets", (torch.int64,)),
+                _dev_ptr(lengths, "lengths", (torch.int32,)),
+                _dev_ptr(dst, "dst", (torch.uint8, torch.int8)),
+                _dev_ptr(dst_offsets, "dst_offsets", (torch.int64,), n),
+                _dev_ptr(out_len, "out_len"), _dev_ptr(status, "status"), n, max_len, int(level),
+                _dev_ptr(scratch, "scratch", (torch.uint8, torch.int8))
+                if scratch is not None else None,
+                scratch.numel() if scratch is not None else 0, _stream_handle(stream, dev))
+        _check("lvkv_zstd_compress_big_device", rc)
+    return dst, dst_offsets, out_len, status
+
+
 READ_OK, READ_CHECKSUM, READ_BAD_TYPE, READ_SNAPPY_LENGTH, READ_SNAPPY_CONTENTS, \
     READ_ZSTD_LENGTH, READ_CAPACITY, READ_TOO_LARGE, READ_ZSTD_CONTENTS = range(9)
 
@@ -757,6 +825,53 @@ def sst_write_blocks(raw, offsets, lengths, *, compression: int = 1, max_len: Op
             _stream_handle(stream, dev))
     _check("lvkv_sst_write_blocks_level_device", rc)
     return file, hoff, hsize, typ, end
+
+
+def sst_write_blocks_status(raw, offsets, lengths, *, compression: int = 1, zstd_level: int = 1,
+                            max_len: Optional[int] = None, file=None, file_offset: int = 0,
+                            stream=None):
+    """sst_write_blocks for blocks of any size, with the codec's verdict per
+    block: snappy compresses every block; zstd (levels <= 2 except 0) every
+    block up to min(max_len, ZSTD_COMPRESS_BIG_MAX_BLOCK). status[i] is
+    ZSTD_OK, or ZSTD_TOO_LARGE for a block the device left raw (type 0) that
+    TableBuilder::WriteBlock would have compressed: a zstd block past that
+    bound. A block the 12.5% rule kept raw has status OK. The scratch grows
+    with the bytes written, not with the block count times max_len. Returns
+    (file, handle offsets int64, handle sizes int32, types uint8, end offset
+    int64 tensor of one, status uint8)."""
+    torch = _torch()
+    n = offsets.numel()
+    dev = raw.device
+    total_raw = int(lengths.to(torch.int64).sum().item()) if n else 0
+    if max_len is None:
+        max_len = int(lengths.max().item()) if n else 0
+    max_len = max(0, min(int(max_len), 0xFFFFFFFF))
+    if file is None:
+        file = torch.zeros(max(1, file_offset + total_raw + 5 * n), dtype=torch.uint8, device=dev)
+    hoff = torch.empty(n, dtype=torch.int64, device=dev)
+    hsize = torch.empty(n, dtype=torch.int32, device=dev)
+    typ = torch.empty(n, dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    end = torch.empty(1, dtype=torch.int64, device=dev)
+    scratch = None
+    if compression in (1, 2) and n:
+        # (the zstd compressor's pool is part of it only for compression 2)
+        need = int(_lib.lvkv_sst_write_scratch_bytes_v2(n, total_raw,
+                                                        max_len if compression == 2 else 0))
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lvkv_sst_write_blocks_status_device(
+            _dev_ptr(raw, "raw", (torch.uint8, torch.int8)) if n else None,
+            _dev_ptr(offsets, "offsets", (torch.int64,)) if n else None,
+            _dev_ptr(lengths, "lengths", (torch.int32,), n) if n else None, n, compression,
+            int(zstd_level), max_len, _dev_ptr(scratch, "scratch") if scratch is not None else None,
+            _dev_ptr(file, "file", (torch.uint8, torch.int8)), file_offset,
+            _dev_ptr(hoff, "hoff") if n else None, _dev_ptr(hsize, "hsize") if n else None,
+            _dev_ptr(typ, "type") if n else None, _dev_ptr(end, "end"),
+            scratch.numel() if scratch is not None else 0,
+            _dev_ptr(status, "status") if n else None, _stream_handle(stream, dev))
+    _check("lvkv_sst_write_blocks_status_device", rc)
+    return file, hoff, hsize, typ, end, status
 
 
 def sst_read_blocks(file, handle_off, handle_size, *, max_ulen: int, verify: bool = True,

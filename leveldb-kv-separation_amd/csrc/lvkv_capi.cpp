@@ -96,6 +96,21 @@ hipError_t launch_zstd_compress(const uint8_t* src, const uint64_t* src_off, con
                                 uint8_t* dst, const uint64_t* dst_off, uint32_t* dst_len,
                                 uint8_t* status, uint32_t nblocks, uint32_t max_len, int level,
                                 uint64_t dst_stride, hipStream_t stream);
+size_t zstd_compress_big_scratch(uint32_t max_len);
+hipError_t launch_zstd_compress_big(const uint8_t* src, const uint64_t* src_off,
+                                    const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                    uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
+                                    uint32_t max_len, int level, uint64_t dst_stride,
+                                    uint8_t* scratch, hipStream_t stream);
+uint64_t sst_write_v2_fixed(size_t nblocks, uint32_t max_len);
+uint64_t sst_write_v2_bytes(size_t nblocks, uint64_t total_raw, uint32_t max_len);
+hipError_t launch_sst_write_blocks_status(const uint8_t* raw, const uint64_t* raw_off,
+                                          const uint32_t* raw_len, uint32_t nblocks,
+                                          int compression, uint32_t max_len, uint8_t* scratch,
+                                          uint64_t scratch_bytes, uint8_t* file,
+                                          uint64_t file_offset, uint64_t* hoff, uint32_t* hsize,
+                                          uint8_t* type, uint64_t* end, int zstd_level,
+                                          uint8_t* status, hipStream_t stream);
 hipError_t launch_sst_read_blocks(const uint8_t* file, const uint64_t* hoff, const uint32_t* hsize,
                                   uint32_t nblocks, uint8_t* out, const uint64_t* out_off,
                                   const uint32_t* out_cap, uint32_t* out_len, uint8_t* status,
@@ -942,6 +957,73 @@ int lvkv_zstd_compress_device(const void* d_src, const uint64_t* d_src_off,
       d_dst_off, d_dst_len, d_status, static_cast<uint32_t>(nblocks), max_len, level, 0,
       static_cast<hipStream_t>(stream));
   return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
+size_t lvkv_zstd_compress_big_scratch_bytes(uint32_t max_len) {
+  return zstd_compress_big_scratch(max_len);
+}
+
+int lvkv_zstd_compress_big_device(const void* d_src, const uint64_t* d_src_off,
+                                  const uint32_t* d_src_len, void* d_dst,
+                                  const uint64_t* d_dst_off, uint32_t* d_dst_len,
+                                  uint8_t* d_status, size_t nblocks, uint32_t max_len, int level,
+                                  void* d_scratch, size_t scratch_bytes, void* stream) {
+  if (nblocks == 0) return LVKV_OK;
+  if (!d_src || !d_src_off || !d_src_len || !d_dst || !d_dst_off || !d_dst_len || !d_status ||
+      nblocks > kMaxBlocksPerLaunch)
+    return LVKV_ERR_INVALID;
+  // (the lengths are on the device: a block can need the scratch whenever
+  // max_len lets one past the first kernel's plan)
+  const size_t need = zstd_compress_big_scratch(max_len);
+  if (need != 0 && (!d_scratch || scratch_bytes < need)) return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  const hipError_t e = launch_zstd_compress_big(
+      static_cast<const uint8_t*>(d_src), d_src_off, d_src_len, static_cast<uint8_t*>(d_dst),
+      d_dst_off, d_dst_len, d_status, static_cast<uint32_t>(nblocks), max_len, level, 0,
+      static_cast<uint8_t*>(d_scratch), static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
+size_t lvkv_sst_write_scratch_bytes_v2(size_t nblocks, uint64_t total_raw_bytes, uint32_t max_len) {
+  return sst_write_v2_bytes(nblocks, total_raw_bytes, max_len);
+}
+
+int lvkv_sst_write_blocks_status_device(const void* d_raw, const uint64_t* d_raw_off,
+                                        const uint32_t* d_raw_len, size_t nblocks, int compression,
+                                        int zstd_level, uint32_t max_len, void* d_scratch,
+                                        void* d_file, uint64_t file_offset,
+                                        uint64_t* d_handle_off, uint32_t* d_handle_size,
+                                        uint8_t* d_type, uint64_t* d_end, size_t scratch_bytes,
+                                        uint8_t* d_status, void* stream) {
+  if (!d_end) return LVKV_ERR_INVALID;  // (nowhere to report even an empty batch)
+  if (nblocks == 0) {  // before every other check: d_end = file_offset, by the layout kernel
+    int rc = LVKV_OK;
+    if (current_ctx(&rc) == nullptr) return rc;
+    const hipError_t e = launch_sst_write_blocks(nullptr, nullptr, nullptr, 0, 0, 0, nullptr,
+                                                 nullptr, file_offset, nullptr, nullptr, nullptr,
+                                                 d_end, 1, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? LVKV_OK : hip_fail(e);
+  }
+  if (compression < 0 || compression > 2) return LVKV_ERR_INVALID;
+  if (compression == 2 && (zstd_level == 0 || zstd_level > 2)) return LVKV_ERR_INVALID;
+  if (!d_raw || !d_raw_off || !d_raw_len || !d_file || !d_handle_off || !d_handle_size ||
+      !d_type || !d_status || nblocks > kMaxBlocksPerLaunch)
+    return LVKV_ERR_INVALID;
+  if (compression != 0 &&
+      (!d_scratch ||
+       scratch_bytes < sst_write_v2_fixed(nblocks, compression == 2 ? max_len : 0u) + 16u))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  const hipError_t e = launch_sst_write_blocks_status(
+      static_cast<const uint8_t*>(d_raw), d_raw_off, d_raw_len, static_cast<uint32_t>(nblocks),
+      compression, max_len, static_cast<uint8_t*>(d_scratch), scratch_bytes,
+      static_cast<uint8_t*>(d_file), file_offset, d_handle_off, d_handle_size, d_type, d_end,
+      zstd_level, d_status, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e);
+  return lvkv_sst_fill_trailers_device(d_file, d_handle_off, d_handle_size, nullptr, nblocks,
+                                       stream);
 }
 
 int lvkv_sst_write_blocks_device(const void* d_raw, const uint64_t* d_raw_off,

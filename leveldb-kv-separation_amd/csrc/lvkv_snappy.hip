@@ -786,6 +786,166 @@ hipError_t launch_sst_write_blocks(const uint8_t* raw, const uint64_t* raw_off,
   return hipGetLastError();
 }
 
+// ---- the writer with ragged scratch and per-block status ----------------------
+
+namespace {
+
+// A block's slot in the ragged scratch: either codec's bound, rounded to 16.
+__host__ __device__ __forceinline__ uint64_t sst_slot_bytes(uint32_t n) {
+  const uint64_t zb = uint64_t{n} + (n >> 8) + (n < (128u << 10) ? ((128u << 10) - n) >> 11 : 0u);
+  const uint64_t sb = uint64_t{32} + n + n / 6u;
+  return ((sb > zb ? sb : zb) + 15u) & ~uint64_t{15};
+}
+
+// Where each block's compressed form goes: an exclusive scan of the slots
+// from `first` (the bytes before it take what a block without room writes).
+// A block whose slot would end past `cap` has no room: it is compressed as
+// an empty block into the spare bytes at 0 and reported by sst_status_kernel.
+// One workgroup, a block a thread a pass.
+__global__ void __launch_bounds__(1024) sst_slots_kernel(const uint32_t* raw_len, uint32_t n,
+                                                         uint64_t first, uint64_t cap,
+                                                         uint64_t* off, uint32_t* elen,
+                                                         uint8_t* noroom) {
+  __shared__ uint64_t wsum[17];
+  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+  uint64_t carry = first;
+  for (uint32_t base = 0; base < n; base += 1024) {
+    const uint32_t i = base + t;
+    const uint32_t L = i < n ? raw_len[i] : 0u;
+    const uint64_t local = i < n ? sst_slot_bytes(L) : 0u;
+    uint64_t incl = local;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      const uint64_t y = shfl_up64(incl, d);
+      if (lane >= d) incl += y;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    if (w == 0) {
+      const uint64_t v = lane < 16 ? wsum[lane] : 0;
+      uint64_t s = v;
+      for (uint32_t d = 1; d < 16; d <<= 1) {
+        const uint64_t y = shfl_up64(s, d);
+        if (lane >= d) s += y;
+      }
+      if (lane < 16) wsum[lane] = s - v;
+      if (lane == 15) wsum[16] = s;
+    }
+    __syncthreads();
+    const uint64_t at = carry + wsum[w] + incl - local;
+    if (i < n) {
+      const bool room = at + local <= cap;
+      off[i] = room ? at : 0u;
+      elen[i] = room ? L : 0u;
+      noroom[i] = room ? 0 : 1;
+    }
+    carry += wsum[16];
+    __syncthreads();
+  }
+}
+
+// The verdict the caller sees, and the one the layout acts on.
+__global__ void __launch_bounds__(256) sst_status_kernel(uint8_t* cst, const uint8_t* noroom,
+                                                         uint32_t n, uint8_t* status) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  uint8_t st = LVKV_SNAPPY_OK;
+  if (cst != nullptr) {
+    st = noroom[i] ? static_cast<uint8_t>(LVKV_SNAPPY_TOO_LARGE) : cst[i];
+    cst[i] = st;
+  }
+  status[i] = st;
+}
+
+// sst_place_kernel with each block's own scratch offset.
+__global__ void __launch_bounds__(256) sst_place_ragged_kernel(const uint8_t* raw, const uint64_t* raw_off,
+                                                               const uint8_t* comp, const uint64_t* comp_off,
+                                                               const uint64_t* hoff, const uint32_t* hsize,
+                                                               const uint8_t* type, uint8_t* file) {
+  const uint32_t b = blockIdx.x, t = threadIdx.x;
+  const uint32_t ty = type[b];
+  const uint8_t* src = ty ? comp + comp_off[b] : raw + raw_off[b];
+  uint8_t* dst = file + hoff[b];
+  const uint32_t n = hsize[b];
+  for (uint32_t k = t; k < n; k += 256) dst[k] = src[k];
+  if (t == 0) dst[n] = static_cast<uint8_t>(ty);
+}
+
+constexpr uint64_t kSstSpare = 16;  // the slot of the blocks without room
+
+uint64_t sst_v2_head(size_t nblocks) {  // off u64, elen u32, clen u32, cst u8, noroom u8
+  return (uint64_t{nblocks} * 18u + 255u) & ~uint64_t{255};
+}
+
+}  // namespace
+
+size_t zstd_compress_big_scratch(uint32_t max_len);
+hipError_t launch_zstd_compress_big(const uint8_t* src, const uint64_t* src_off,
+                                    const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                    uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
+                                    uint32_t max_len, int level, uint64_t dst_stride,
+                                    uint8_t* scratch, hipStream_t stream);
+
+// The part of the v2 scratch that does not hold compressed blocks: alignment
+// slack, the per-block arrays, the zstd compressor's pool.
+uint64_t sst_write_v2_fixed(size_t nblocks, uint32_t max_len) {
+  return 256u + sst_v2_head(nblocks) + ((zstd_compress_big_scratch(max_len) + 255u) & ~uint64_t{255});
+}
+
+uint64_t sst_write_v2_bytes(size_t nblocks, uint64_t total_raw, uint32_t max_len) {
+  // sum of slots <= total + total / 6 + 79 a block (either bound + rounding)
+  return sst_write_v2_fixed(nblocks, max_len) + kSstSpare + total_raw + total_raw / 6u +
+         uint64_t{nblocks} * 80u;
+}
+
+hipError_t launch_sst_write_blocks_status(const uint8_t* raw, const uint64_t* raw_off,
+                                          const uint32_t* raw_len, uint32_t nblocks,
+                                          int compression, uint32_t max_len, uint8_t* scratch,
+                                          uint64_t scratch_bytes, uint8_t* file,
+                                          uint64_t file_offset, uint64_t* hoff, uint32_t* hsize,
+                                          uint8_t* type, uint64_t* end, int zstd_level,
+                                          uint8_t* status, hipStream_t stream) {
+  uint32_t* clen = nullptr;
+  uint8_t *cst = nullptr, *noroom = nullptr, *area = nullptr;
+  uint64_t* off = nullptr;
+  if (compression != 0) {
+    uint8_t* base = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(scratch) + 255u) &
+                                               ~uintptr_t{255});
+    const uint64_t slack = static_cast<uint64_t>(base - scratch);
+    off = reinterpret_cast<uint64_t*>(base);
+    uint32_t* elen = reinterpret_cast<uint32_t*>(off + nblocks);
+    clen = elen + nblocks;
+    cst = reinterpret_cast<uint8_t*>(clen + nblocks);
+    noroom = cst + nblocks;
+    uint8_t* zs = base + sst_v2_head(nblocks);
+    const uint64_t zbytes =
+        compression == 2 ? (zstd_compress_big_scratch(max_len) + 255u) & ~uint64_t{255} : 0u;
+    area = zs + zbytes;
+    const uint64_t used = slack + sst_v2_head(nblocks) + zbytes;  // (the caller checked: <= bytes - spare)
+    hipLaunchKernelGGL(sst_slots_kernel, dim3(1), dim3(1024), 0, stream, raw_len, nblocks,
+                       kSstSpare, scratch_bytes - used, off, elen, noroom);
+    if (compression == 1) {
+      CompressArgs a{raw, raw_off, elen, area, off, clen, cst, nblocks, kFrag};
+      const uint32_t in_bytes = (kFrag + 16u + 15u) & ~15u;
+      uint32_t t = 256;
+      while (t < kMaxTable && t < kFrag) t <<= 1;
+      const size_t lds = in_bytes + 1024u + 2u * t;
+      hipLaunchKernelGGL(snappy_compress_kernel, dim3(nblocks), dim3(64), lds, stream, a);
+    } else {
+      const hipError_t e = launch_zstd_compress_big(raw, raw_off, elen, area, off, clen, cst,
+                                                    nblocks, max_len, zstd_level, 0, zs, stream);
+      if (e != hipSuccess) return e;
+    }
+  }
+  hipLaunchKernelGGL(sst_status_kernel, dim3((nblocks + 255u) / 256u), dim3(256), 0, stream, cst,
+                     noroom, nblocks, status);
+  hipLaunchKernelGGL(sst_layout_kernel, dim3(1), dim3(1024), 0, stream, raw_len, clen, cst,
+                     nblocks, file_offset, hoff, hsize, type, end,
+                     static_cast<uint32_t>(compression == 2 ? 2 : 1));
+  hipLaunchKernelGGL(sst_place_ragged_kernel, dim3(nblocks), dim3(256), 0, stream, raw, raw_off,
+                     area, off, hoff, hsize, type, file);
+  return hipGetLastError();
+}
+
 hipError_t launch_sst_read_blocks(const uint8_t* file, const uint64_t* hoff, const uint32_t* hsize,
                                   uint32_t nblocks, uint8_t* out, const uint64_t* out_off,
                                   const uint32_t* out_cap, uint32_t* out_len, uint8_t* status,

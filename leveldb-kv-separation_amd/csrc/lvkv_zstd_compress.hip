@@ -28,6 +28,11 @@
 // (Huffman codes 16 lanes a stream with atomic ORs into LDS words, FSE table
 // spreads by ballot ranks); the wave runs the tree build, the normalisation
 // and the three interleaved FSE state chains.
+//
+// Blocks past that LDS plan, up to one Zstd block (128 KiB), are a second
+// kernel's (zstd_compress_big_kernel, below): the same code on
+// a block kept in an HBM scratch slot, the hash table and the frame's body
+// in LDS.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -1483,11 +1488,36 @@ __device__ __forceinline__ void store_seq(Seqs& s, const uint8_t* in, uint32_t a
   s.nseq += 1u;
 }
 
+// The sequences of a block past the LDS plan (up to 128 KiB), in HBM: two
+// words a sequence -- litLength (17 bits) | the low 15 bits of mlBase << 17,
+// then offset code + 1 (18 bits) | the top 2 bits of mlBase << 18. The
+// lengths are kept whole: zstd's own store truncates them to 16 bits and
+// marks the one sequence a block can hold with litLength or mlBase >= 65,536
+// (longLengthID), whose code becomes MaxLL (35) or MaxML (52); ll_code and
+// ml_code of the whole value give the same codes, and the 16 extra bits are
+// the value's low 16 bits either way.
+struct SeqsBig {
+  uint8_t* lits;
+  uint32_t* sq;
+  uint32_t nlit, nseq;
+};
+
+__device__ __forceinline__ void store_seq(SeqsBig& s, const uint8_t* in, uint32_t anchor, uint32_t litlen,
+                                          uint32_t offcode, uint32_t mlbase, uint32_t lane) {
+  for (uint32_t k = lane; k < litlen; k += 64) s.lits[s.nlit + k] = in[anchor + k];
+  if (lane == 0) {
+    s.sq[2u * s.nseq] = litlen | (mlbase << 17);
+    s.sq[2u * s.nseq + 1u] = (offcode + 1u) | ((mlbase >> 15) << 18);
+  }
+  s.nlit += litlen;
+  s.nseq += 1u;
+}
+
 // ZSTD_compressBlock_fast_generic over the whole frame in[0, n) (one block:
 // n <= the window), 64 steps a window.
-template <typename TIdx>
+template <typename TIdx, typename TSeq = Seqs>
 __device__ __forceinline__ void match_block(const uint8_t* in, uint32_t n, TIdx* table, uint32_t* tags,
-                            const ZParams& zp, Seqs& sq, uint32_t lane) {
+                            const ZParams& zp, TSeq& sq, uint32_t lane) {
   const uint32_t hlog = zp.hlog, mls = zp.mls;
   const uint32_t ss = zp.tl + (zp.tl ? 0u : 1u) + 1u;
   const int32_t ilimit = static_cast<int32_t>(n) - 8;
@@ -1889,6 +1919,247 @@ __global__ void __launch_bounds__(64) zstd_compress_kernel(ZcArgs a) {
 #endif
 }
 
+// ---- blocks past the LDS plan: 20,481 - 131,072 bytes -------
+//
+// One Zstd block a frame still (ZSTD_BLOCKSIZE_MAX = 128 KiB), the same
+// match finder and entropy coders, another home for the data: the hash table
+// (u32 entries, up to 2^15 of them) and the window slots stay in LDS; the
+// block -- a padded copy, so that the 4- and 8-byte reads behave as on the
+// LDS copy and no frame byte depends on what follows the block in the
+// caller's buffer -- its literals, its sequences and their codes live in a
+// scratch slot in HBM. The frame's body is assembled in LDS over the dead
+// hash table. A fixed pool of slots, one a workgroup: the grid is persistent
+// and pulls the blocks the first kernel marked TOO_LARGE off a counter.
+
+constexpr uint32_t kBigCus = 256;       // the persistent grid: a workgroup a CU, or two (big_slots)
+constexpr uint32_t kBigHead = 256;      // the scratch's header: the work counter
+constexpr uint32_t kBigMax = LVKV_ZSTD_COMPRESS_BIG_MAX_BLOCK;
+
+struct ZcBigArgs {
+  const uint8_t* src;
+  const uint64_t* src_off;
+  const uint32_t* src_len;
+  uint8_t* dst;
+  const uint64_t* dst_off;
+  uint32_t* dst_len;
+  uint8_t* status;
+  uint32_t nblocks;
+  int32_t level;
+  uint32_t small_max;  // the first kernel's max_len: longer blocks are this kernel's
+  uint32_t cap;        // min(max_len, kBigMax): longer blocks stay TOO_LARGE
+  uint64_t dst_stride;
+  uint32_t* counter;   // the next block index to look at
+  uint8_t* slots;      // a slot a workgroup: zstd_big_slots(cap) x slot_bytes
+  uint64_t slot_bytes;
+  uint32_t s_lit, s_seq, s_code, smax;  // offsets in a slot (the block's copy at 0)
+  uint32_t o_ent, o_tag;                // LDS offsets (table / frame body at 0)
+  uint32_t level_ok;                    // the level is a ZSTD_fast one at these sizes
+};
+
+// Everything this wave wrote to HBM is visible to its later reads (other
+// lanes' included): the HBM-side counterpart of lds_sync().
+__device__ __forceinline__ void hbm_sync() {
+  __threadfence();
+  lds_sync();
+}
+
+// The block's copy: dst[0, n) = src[0, n), then 16 zero bytes (up to the
+// dword). dst is dword-aligned; src is read in aligned dwords that hold at
+// least one byte of the block.
+__device__ __forceinline__ void stage_big(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
+  const uint32_t mis = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(src)) & 3u;
+  const uint32_t* s = reinterpret_cast<const uint32_t*>(src - mis);
+  const uint32_t nd = (n + 3u) >> 2, ndp = (n + 16u + 3u) >> 2;
+  for (uint32_t i = lane; i < ndp; i += 64) {
+    uint32_t v = 0;
+    if (i < nd) {
+      const uint32_t lo = s[i];
+      const uint32_t hi = (mis != 0 && 4u * (i + 1u) < mis + n) ? s[i + 1] : 0u;
+      v = __builtin_amdgcn_alignbyte(hi, lo, mis);
+      const uint32_t rem = n - 4u * i;
+      if (rem < 4u) v &= (1u << (8u * rem)) - 1u;
+    }
+    reinterpret_cast<uint32_t*>(dst)[i] = v;
+  }
+}
+
+__device__ __forceinline__ void zc_big_block(const ZcBigArgs& a, uint32_t b, uint32_t n, uint8_t* slot,
+                                             uint8_t* smem, uint32_t lane, uint64_t* stamp) {
+  const uint8_t* src = a.src + a.src_off[b];
+  uint8_t* g = a.dst + (a.dst_off ? a.dst_off[b] : b * a.dst_stride);
+  auto finish = [&](uint32_t st, uint32_t len) {
+    if (lane == 0) {
+      a.dst_len[b] = len;
+      a.status[b] = static_cast<uint8_t>(st);
+    }
+  };
+  const ZParams zp = zstd_port_params(a.level, n);
+  if (!zp.ok) return finish(LVKV_ZSTD_UNSUPPORTED, 0);
+  const uint32_t fh = frame_header(g, zp.wlog, n, lane);
+  const uint8_t* in = slot;
+  auto raw_block = [&]() {
+    const uint32_t bh = 1u + (n << 3);  // (21 bits of size: n <= 128 KiB)
+    if (lane < 3) g[fh + lane] = static_cast<uint8_t>(bh >> (8u * lane));
+    for (uint32_t k = lane; k < n; k += 64) g[fh + 3u + k] = in[k];
+    finish(LVKV_ZSTD_OK, fh + 3u + n);
+  };
+  uint32_t* table = reinterpret_cast<uint32_t*>(smem);
+  uint32_t* tags = reinterpret_cast<uint32_t*>(smem + a.o_tag);
+  SeqsBig sq;
+  sq.lits = slot + a.s_lit;
+  sq.sq = reinterpret_cast<uint32_t*>(slot + a.s_seq);
+  sq.nlit = 0;
+  sq.nseq = 0;
+  stage_big(slot, src, n, lane);
+  for (uint32_t k = lane; k < (1u << zp.hlog); k += 64) table[k] = 0;
+  for (uint32_t k = lane; k < kTags; k += 64) tags[k] = 0xFFFFFFFFu;
+  hbm_sync();
+  match_block<uint32_t, SeqsBig>(in, n, table, tags, zp, sq, lane);
+  hbm_sync();
+  // ---- entropy: the body in LDS over the dead table
+  uint8_t* out = smem;
+  uint8_t* ent = smem + a.o_ent;
+  HNode* nodes = reinterpret_cast<HNode*>(tags);
+  const uint32_t nseq = sq.nseq;
+  const uint32_t limit = n - ((n >> 6) + 2u);
+  uint32_t pos = compress_literals(out, sq.lits, sq.nlit, zp.tl > 0, ent, nodes, lane, stamp);
+  if (pos + 1u >= limit) return raw_block();
+  if (lane == 0) {
+    if (nseq < 128) {
+      out[pos] = static_cast<uint8_t>(nseq);
+    } else if (nseq < 0x7F00) {
+      out[pos] = static_cast<uint8_t>((nseq >> 8) + 0x80u);
+      out[pos + 1] = static_cast<uint8_t>(nseq);
+    } else {
+      out[pos] = 0xFF;
+      out[pos + 1] = static_cast<uint8_t>(nseq - 0x7F00u);
+      out[pos + 2] = static_cast<uint8_t>((nseq - 0x7F00u) >> 8);
+    }
+  }
+  pos += nseq < 128 ? 1u : (nseq < 0x7F00 ? 2u : 3u);
+  lds_sync();
+  if (nseq > 0) {
+    uint8_t* llc = slot + a.s_code;
+    uint8_t* ofc = llc + round16(a.smax);
+    uint8_t* mlc = ofc + round16(a.smax);
+    auto unpack = [&](uint32_t k, uint32_t* ll, uint32_t* mlb, uint32_t* of) {
+      const uint32_t w0 = sq.sq[2u * k], w1 = sq.sq[2u * k + 1u];
+      *ll = w0 & 0x1FFFFu;
+      *mlb = (w0 >> 17) | ((w1 >> 18) << 15);
+      *of = w1 & 0x3FFFFu;
+    };
+    for (uint32_t i = lane; i < nseq; i += 64) {
+      uint32_t ll, mlb, of;
+      unpack(i, &ll, &mlb, &of);
+      llc[i] = static_cast<uint8_t>(ll_code(ll));
+      ofc[i] = static_cast<uint8_t>(hibit(of));
+      mlc[i] = static_cast<uint8_t>(ml_code(mlb));
+    }
+    hbm_sync();
+    const uint32_t seq_head = pos++;
+    BitW bw;
+    bw_init(bw, out, pos);
+    FseC tll, tof, tml;
+    uint32_t at_ll, at_of, at_ml;
+    const uint32_t ty_ll = seq_table(0, llc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStLL),
+                                     bw, &tll, &at_ll, lane);
+    const uint32_t ty_of = seq_table(1, ofc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStOF),
+                                     bw, &tof, &at_of, lane);
+    const uint32_t ty_ml = seq_table(2, mlc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStML),
+                                     bw, &tml, &at_ml, lane);
+    const uint32_t last_nc = at_ml != 0xFFFFFFFFu ? at_ml : (at_of != 0xFFFFFFFFu ? at_of : at_ll);
+    if (lane == 0) out[seq_head] = static_cast<uint8_t>((ty_ll << 6) + (ty_of << 4) + (ty_ml << 2));
+    lds_sync();
+    const uint32_t bs_start = bw_end(bw);
+    bw_init(bw, out, bs_start);
+    // 64 sequences at a time in registers, as the first kernel
+    uint32_t base = (nseq - 1u) & ~63u;
+    uint32_t rl = 0, rm = 0, ro = 0, rc = 0;
+    auto load = [&](uint32_t b0) {
+      const uint32_t k = b0 + lane;
+      rl = rm = ro = rc = 0;
+      if (k < nseq) {
+        unpack(k, &rl, &rm, &ro);
+        rc = llc[k] | (static_cast<uint32_t>(ofc[k]) << 8) | (static_cast<uint32_t>(mlc[k]) << 16);
+      }
+    };
+    load(base);
+    uint32_t i = nseq - 1u;
+    uint32_t ll = __builtin_amdgcn_readlane(rl, i - base), mlb = __builtin_amdgcn_readlane(rm, i - base);
+    uint32_t of = __builtin_amdgcn_readlane(ro, i - base), cc = __builtin_amdgcn_readlane(rc, i - base);
+    uint32_t cl = cc & 255u, co = (cc >> 8) & 255u, cm = cc >> 16;
+    uint32_t sm = fse_init(tml, cm), so = fse_init(tof, co), sl = fse_init(tll, cl);
+    bw_add(bw, ll, ll_bits(cl), lane);
+    bw_add(bw, mlb, ml_bits(cm), lane);
+    bw_add(bw, of, co, lane);
+    bool over = false;
+    while (i > 0) {
+      --i;
+      if (i < base) {
+        base -= 64u;
+        load(base);
+      }
+      ll = __builtin_amdgcn_readlane(rl, i - base);
+      mlb = __builtin_amdgcn_readlane(rm, i - base);
+      of = __builtin_amdgcn_readlane(ro, i - base);
+      cc = __builtin_amdgcn_readlane(rc, i - base);
+      cl = cc & 255u;
+      co = (cc >> 8) & 255u;
+      cm = cc >> 16;
+      so = fse_enc(tof, so, co, bw, lane);
+      sm = fse_enc(tml, sm, cm, bw, lane);
+      sl = fse_enc(tll, sl, cl, bw, lane);
+      bw_add(bw, ll, ll_bits(cl), lane);
+      bw_add(bw, mlb, ml_bits(cm), lane);
+      bw_add(bw, of, co, lane);
+      if (4u * bw.d >= limit) {
+        over = true;
+        break;
+      }
+    }
+    if (over) return raw_block();
+    bw_add(bw, sm, tml.log, lane);
+    bw_add(bw, so, tof.log, lane);
+    bw_add(bw, sl, tll.log, lane);
+    bw_add(bw, 1u, 1, lane);
+    bw_flush(bw, lane);
+    pos = bw_end(bw);
+    if (last_nc != 0xFFFFFFFFu && pos - last_nc < 4u) return raw_block();
+  }
+  if (pos >= limit) return raw_block();
+  lds_sync();
+  const uint32_t bh = 1u + (2u << 1) + (pos << 3);
+  if (lane < 3) g[fh + lane] = static_cast<uint8_t>(bh >> (8u * lane));
+  for (uint32_t k = lane; k < pos; k += 64) g[fh + 3u + k] = out[k];
+  finish(LVKV_ZSTD_OK, fh + 3u + pos);
+}
+
+__global__ void __launch_bounds__(64) zstd_compress_big_kernel(ZcBigArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const uint32_t lane = threadIdx.x;
+  uint8_t* slot = a.slots + blockIdx.x * a.slot_bytes;
+#ifdef LVKV_PROBE_BUILD
+  __shared__ uint64_t stamp_lds[16];  // (compress_literals' phase stamps: not reported)
+  uint64_t* stamp = stamp_lds;
+#else
+  uint64_t* stamp = nullptr;
+#endif
+  for (;;) {
+    uint32_t b = 0;
+    if (lane == 0) b = atomicAdd(a.counter, 1u);
+    b = uni(b);
+    if (b >= a.nblocks) return;
+    const uint32_t n = a.src_len[b];
+    if (n > a.cap) {  // (level 2 past 128 KiB is not ZSTD_fast: the first kernel's UNSUPPORTED)
+      if (a.level_ok && lane == 0) a.status[b] = LVKV_ZSTD_TOO_LARGE;
+      continue;
+    }
+    if (a.status[b] != LVKV_ZSTD_TOO_LARGE || n <= a.small_max) continue;
+    lds_sync();  // (the last block's body has left the LDS)
+    zc_big_block(a, b, n, slot, smem, lane, stamp);
+  }
+}
+
 }  // namespace
 
 struct ZstdCompressPlan {
@@ -1945,6 +2216,85 @@ hipError_t launch_zstd_compress(const uint8_t* src, const uint64_t* src_off, con
   ZcArgs a{src, src_off, src_len, dst, dst_off, dst_len, status, nblocks, level, max_len,
            dst_stride, p.o_tbl, p.o_tag, p.o_lit, p.o_sll, p.o_sof, p.smax, g_zstdc_stamps};
   hipLaunchKernelGGL(zstd_compress_kernel<uint16_t>, dim3(nblocks), dim3(64), p.lds, stream, a);
+  return hipGetLastError();
+}
+
+// ---- the call that takes blocks up to 128 KiB --------------------------------
+
+struct ZstdBigPlan {
+  uint32_t lds, o_ent, o_tag;            // LDS: table / body at 0, entropy scratch, window slots
+  uint32_t s_lit, s_seq, s_code, smax;   // a scratch slot: the block's copy at 0
+  uint64_t slot_bytes;
+};
+
+// cap in (LVKV_ZSTD_COMPRESS_MAX_BLOCK, LVKV_ZSTD_COMPRESS_BIG_MAX_BLOCK].
+// 142,208 bytes of LDS at 128 KiB (one workgroup a CU), 623 KB a slot.
+ZstdBigPlan zstd_big_plan(uint32_t cap, int level) {
+  ZstdBigPlan p{};
+  uint32_t hmax = 6;
+  for (uint32_t n : {20481u, 32768u, 32769u, 65536u, 65537u, 131072u}) {
+    const ZParams z = zstd_port_params(level, n < cap ? n : cap);
+    if (z.ok && z.hlog > hmax) hmax = z.hlog;
+  }
+  p.smax = cap / 4u + 2u;
+  const uint32_t body = round16(cap + 512u);
+  p.o_ent = (4u << hmax) > body ? (4u << hmax) : body;
+  p.o_tag = p.o_ent + round16(kECodes);
+  p.lds = p.o_tag + 4u * kTags;
+  p.s_lit = round16(cap + 16u + 4u);
+  p.s_seq = p.s_lit + round16(cap);
+  p.s_code = p.s_seq + 8u * round16(p.smax);
+  p.slot_bytes = (uint64_t{p.s_code} + 3u * round16(p.smax) + 255u) & ~uint64_t{255};
+  return p;
+}
+
+// The persistent grid at `level`: two workgroups a CU where two LDS plans
+// share the 160 KB (blocks up to 64 KiB or so at levels 1 and below: level
+// 2's hash table alone is 128 KiB), else one.
+uint32_t zstd_big_grid(uint32_t cap, int level) {
+  return 2u * zstd_big_plan(cap, level).lds <= 160u * 1024u ? 2u * kBigCus : kBigCus;
+}
+
+// The slots, one a workgroup of the largest grid any level gets (level 1's:
+// the size is the same for every level and every batch).
+uint32_t zstd_big_slots(uint32_t cap) { return zstd_big_grid(cap, 1); }
+
+// Independent of the batch: the counter and the slots (+ the slack that
+// aligns them). 0 when no block can need it.
+size_t zstd_compress_big_scratch(uint32_t max_len) {
+  if (max_len <= LVKV_ZSTD_COMPRESS_MAX_BLOCK) return 0;
+  const uint32_t cap = max_len < kBigMax ? max_len : kBigMax;
+  return 256u + kBigHead + size_t{zstd_big_slots(cap)} * zstd_big_plan(cap, 1).slot_bytes;
+}
+
+// launch_zstd_compress for the blocks its LDS plan holds, then -- same stream
+// -- the persistent grid for those it marked, up to min(max_len, 128 KiB).
+// scratch: zstd_compress_big_scratch(max_len) bytes (the caller checked).
+hipError_t launch_zstd_compress_big(const uint8_t* src, const uint64_t* src_off,
+                                    const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                    uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
+                                    uint32_t max_len, int level, uint64_t dst_stride,
+                                    uint8_t* scratch, hipStream_t stream) {
+  const uint32_t small_max =
+      max_len < LVKV_ZSTD_COMPRESS_MAX_BLOCK ? max_len : LVKV_ZSTD_COMPRESS_MAX_BLOCK;
+  hipError_t e = launch_zstd_compress(src, src_off, src_len, dst, dst_off, dst_len, status, nblocks,
+                                      small_max, level, dst_stride, stream);
+  if (e != hipSuccess || nblocks == 0 || max_len <= LVKV_ZSTD_COMPRESS_MAX_BLOCK) return e;
+  const uint32_t cap = max_len < kBigMax ? max_len : kBigMax;
+  const ZstdBigPlan p = zstd_big_plan(cap, level);
+  uint8_t* base = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(scratch) + 255u) &
+                                             ~uintptr_t{255});
+  e = hipMemsetAsync(base, 0, kBigHead, stream);
+  if (e != hipSuccess) return e;
+  ZcBigArgs a{src, src_off, src_len, dst, dst_off, dst_len, status, nblocks, level, small_max, cap,
+              dst_stride, reinterpret_cast<uint32_t*>(base), base + kBigHead, p.slot_bytes,
+              p.s_lit, p.s_seq, p.s_code, p.smax, p.o_ent, p.o_tag,
+              zstd_port_params(level, 1).ok};
+  const uint32_t slots = zstd_big_slots(cap);
+  const uint32_t lg = zstd_big_grid(cap, level);
+  const uint32_t wgs = lg < slots ? lg : slots;  // (a workgroup never leaves the pool)
+  const uint32_t grid = nblocks < wgs ? nblocks : wgs;
+  hipLaunchKernelGGL(zstd_compress_big_kernel, dim3(grid), dim3(64), p.lds, stream, a);
   return hipGetLastError();
 }
 

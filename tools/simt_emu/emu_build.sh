@@ -1,7 +1,9 @@
 #!/bin/bash
 # Builds the CPU SIMT emulation of the device Zstd compressor (debugging aid,
 # not part of the product): the kernel source compiled by g++ against
-# tools/simt_emu/hip/hip_runtime.h, with AddressSanitizer. Output:
+# tools/simt_emu/hip/hip_runtime.h, with AddressSanitizer and UBSan (both
+# kernels: zstdc_emu takes the call for blocks up to 128 KiB when MAX_LEN is
+# past 20480). Output:
 # build/simt_emu/zstdc_emu (see zstdc_emu.cc; tools/simt_emu/zstdc_check.py).
 set -euo pipefail
 HERE=$(cd "$(dirname "$0")" && pwd)

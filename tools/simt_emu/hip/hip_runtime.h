@@ -136,3 +136,5 @@ inline void launch(K kernel, dim3 grid, size_t lds, A... args) {
 #define atomicOr(p, v) __atomic_fetch_or((p), (v), __ATOMIC_SEQ_CST)
 #define hipLaunchKernelGGL(k, grid, block, lds, stream, ...) emu::launch(k, grid, lds, __VA_ARGS__)
 #define hipGetLastError() 0
+#define hipMemsetAsync(p, v, n, stream) (memset((p), (v), (n)), 0)
+#define __threadfence() ((void)0)

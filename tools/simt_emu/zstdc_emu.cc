@@ -2,6 +2,10 @@
 //   zstdc_emu IN.bin LENS.u32 LEVEL MAX_LEN OUT.bin OUTLENS.u32
 // Compresses the blocks (lengths in LENS, packed in IN) one emulated
 // workgroup at a time; writes the frames packed, their lengths and statuses.
+// MAX_LEN past 20480 drives the call for blocks up to 128 KiB (the second
+// kernel, its scratch a malloc of exactly the size the C-ABI asks for). The
+// blocks are packed with nothing between them and the last one ends the
+// input allocation, so AddressSanitizer sees any read past a block's dword.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,6 +17,12 @@ hipError_t launch_zstd_compress(const uint8_t* src, const uint64_t* src_off, con
                                 uint8_t* dst, const uint64_t* dst_off, uint32_t* dst_len,
                                 uint8_t* status, uint32_t nblocks, uint32_t max_len, int level,
                                 uint64_t dst_stride, hipStream_t stream);
+size_t zstd_compress_big_scratch(uint32_t max_len);
+hipError_t launch_zstd_compress_big(const uint8_t* src, const uint64_t* src_off,
+                                    const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                    uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
+                                    uint32_t max_len, int level, uint64_t dst_stride,
+                                    uint8_t* scratch, hipStream_t stream);
 }
 
 static std::vector<uint8_t> slurp(const char* p) {
@@ -45,8 +55,18 @@ int main(int argc, char** argv) {
   in.resize(p + 64);
   std::vector<uint8_t> dst(q + 64), st(n);
   std::vector<uint32_t> dl(n);
-  lvkv::launch_zstd_compress(in.data(), off.data(), len.data(), dst.data(), doff.data(), dl.data(),
-                             st.data(), n, max_len, level, 0, nullptr);
+  if (max_len <= 20480) {
+    lvkv::launch_zstd_compress(in.data(), off.data(), len.data(), dst.data(), doff.data(),
+                               dl.data(), st.data(), n, max_len, level, 0, nullptr);
+  } else {
+    std::vector<uint8_t> scratch(lvkv::zstd_compress_big_scratch(max_len));
+    const size_t exact = (p + 3) & ~uint64_t{3};  // the kernels read whole aligned dwords
+    uint8_t* src = static_cast<uint8_t*>(malloc(exact ? exact : 4));
+    memcpy(src, in.data(), exact);
+    lvkv::launch_zstd_compress_big(src, off.data(), len.data(), dst.data(), doff.data(), dl.data(),
+                                   st.data(), n, max_len, level, 0, scratch.data(), nullptr);
+    free(src);
+  }
   FILE* fo = fopen(argv[5], "wb");
   FILE* fl = fopen(argv[6], "wb");
   for (uint32_t i = 0; i < n; ++i) {

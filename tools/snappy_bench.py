@@ -11,6 +11,10 @@ whole batch in one launch, timed with HIP events on the launch stream. The
 CPU lines run libsnappy 1.1.8 (the library the reference would link) the
 db_bench way on one thread, and in 16 processes over distinct blocks (run
 before the GPU is initialised: the pool forks).
+The zstd_compress_64k / _128k lines: `--big-blocks` (4,096) blocks of 64 KiB
+and of 128 KiB at level 1 through lvkv_zstd_compress_big_device, next to
+libzstd 1.4.9 through the port's calls on the same bytes (one core, 16
+processes) in the same run.
 Prints one JSON line; writes gpurun_out/snappy_bench.json.
 """
 from __future__ import annotations
@@ -92,10 +96,11 @@ def zstd_cpu_lines(frames, seconds: float = 2.0, procs: int = 16):
     return {k: round(v, 1) for k, v in res.items()}
 
 
-def zstd_compress_cpu_lines(blocks: np.ndarray, seconds: float = 2.0, procs: int = 16):
-    """libzstd 1.4.9 through port::Zstd_Compress's calls, per 4 KiB block at
-    level 1 (oracle/zstd_port_bench, a C harness): one core and `procs`
-    processes."""
+def zstd_compress_cpu_lines(blocks: np.ndarray, seconds: float = 2.0, procs: int = 16,
+                            block_bytes: int = 4096):
+    """libzstd 1.4.9 through port::Zstd_Compress's calls, per block of
+    block_bytes (4 KiB by default) at level 1 (oracle/zstd_port_bench, a C
+    harness): one core and `procs` processes."""
     import subprocess
     import tempfile
     exe = REPO / "oracle" / "zstd_port_bench"
@@ -106,7 +111,7 @@ def zstd_compress_cpu_lines(blocks: np.ndarray, seconds: float = 2.0, procs: int
         f.flush()
         res = {}
         for p in (1, procs):
-            out = subprocess.run([str(exe), f.name, "4096", "1", str(seconds), str(p)],
+            out = subprocess.run([str(exe), f.name, str(block_bytes), "1", str(seconds), str(p)],
                                  capture_output=True, text=True, check=True).stdout
             r = json.loads(out)
             res[f"comp_{'1t' if p == 1 else f'{p}p'}_MBps"] = r["MBps"]
@@ -156,6 +161,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--big-blocks", type=int, default=4096,
+                    help="blocks a launch of the 64 KiB and 128 KiB zstd compress lines (0: skip)")
+    ap.add_argument("--big-steps", type=int, default=5)
     ap.add_argument("--zstd-frames", default=None,
                     help="read the zstd frames from this file instead of libzstd (profiled "
                          "runs: the profiler's own zstd clashes with the library)")
@@ -187,6 +195,11 @@ def main():
         return
     zcpu = None if args.no_cpu or zframes is None else zstd_cpu_lines(zframes)
     zccpu = None if args.no_cpu else zstd_compress_cpu_lines(block_batch(256))
+    # the library on the large blocks (64 of each size: the generator's data
+    # is 1 MiB, cycled), before the GPU is initialised like the other CPU lines
+    big_sizes = (65536, 131072) if args.big_blocks > 0 else ()
+    zccpu_big = {Lb: None if args.no_cpu else
+                 zstd_compress_cpu_lines(block_batch(64, Lb), block_bytes=Lb) for Lb in big_sizes}
     import torch
     import __graft_entry__ as g
     lvkv = g.load_package()
@@ -294,6 +307,47 @@ def main():
                             "output_pct": round(100.0 * zc_bytes / raw, 2), "level": 1}
     if zccpu is not None:
         res["cpu_libzstd_1_4_9_port_compress"] = zccpu
+    # zstd compress on blocks past the first kernel's LDS plan: --big-blocks
+    # blocks of 64 KiB and of 128 KiB, level 1, through the call for blocks up
+    # to 128 KiB (its second, persistent kernel), next to the library on the
+    # same bytes in this same run
+    del zdst, udst, dst
+    for Lb in big_sizes:
+        nbb = args.big_blocks
+        bhost = block_batch(nbb, Lb)
+        bsrc = torch.from_numpy(bhost).to(dev)
+        boff = torch.arange(nbb, dtype=torch.int64, device=dev) * Lb
+        bln = torch.full((nbb,), Lb, dtype=torch.int32, device=dev)
+        bb = int(lvkv.zstd_compress_bound(Lb))
+        bdst = torch.empty(nbb * bb, dtype=torch.uint8, device=dev)
+        bdoff = torch.arange(nbb, dtype=torch.int64, device=dev) * bb
+        blen = torch.empty(nbb, dtype=torch.int32, device=dev)
+        bst = torch.empty(nbb, dtype=torch.uint8, device=dev)
+        scr = torch.empty(lvkv.zstd_compress_big_scratch_bytes(Lb), dtype=torch.uint8, device=dev)
+        steps, warm = args.steps, args.warmup
+        args.steps, args.warmup = args.big_steps, 1
+        t_b = timed(lambda: lvkv.lib.lvkv_zstd_compress_big_device(
+            bsrc.data_ptr(), boff.data_ptr(), bln.data_ptr(), bdst.data_ptr(), bdoff.data_ptr(),
+            blen.data_ptr(), bst.data_ptr(), nbb, Lb, 1, scr.data_ptr(), scr.numel(),
+            stream.cuda_stream))
+        args.steps, args.warmup = steps, warm
+        torch.cuda.synchronize()
+        assert int(bst.max()) == 0
+        b_bytes = int(blen.to(torch.int64).sum())
+        bh = bdst.cpu().numpy()
+        for i in range(0, nbb, max(1, nbb // 8)):  # parity on a sample (the tests cover the rest)
+            blk = bhost[i * Lb:(i + 1) * Lb].tobytes()
+            want = ze.lib_port_compress(zlib_w, blk, 1) if zlib_w else ze.compress(blk, 1)
+            assert bh[i * bb:i * bb + int(blen[i])].tobytes() == want, (Lb, i)
+        braw = nbb * Lb
+        key = f"zstd_compress_{Lb // 1024}k"
+        res[key] = {"blocks": nbb, "block_bytes": Lb, "us_per_launch": round(t_b * 1e6, 1),
+                    "GBps_uncompressed": round(braw / t_b / 1e9, 3),
+                    "output_pct": round(100.0 * b_bytes / braw, 2), "level": 1,
+                    "scratch_MB": round(scr.numel() / 1e6, 1)}
+        if zccpu_big[Lb] is not None:
+            res[key]["cpu_libzstd_1_4_9_port_compress"] = zccpu_big[Lb]
+        del bsrc, bdst, scr
     print(json.dumps(res), flush=True)
     (REPO / "gpurun_out").mkdir(exist_ok=True)
     (REPO / "gpurun_out" / "snappy_bench.json").write_text(json.dumps(res, indent=1))
