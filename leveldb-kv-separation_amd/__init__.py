@@ -790,6 +790,54 @@ def zstd_uncompress(src, offsets, lengths, *, max_ulen: int, dst=None, dst_offse
     return dst, dst_offsets, out_len, status
 
 
+def _sst_write(raw, offsets, lengths, compression, zstd_level, max_len, file, file_offset, stream,
+               with_status):
+    """Both writers: the outputs, the scratch by the public sizing function of
+    the call (fixed stride, or ragged with a status), the call."""
+    torch = _torch()
+    n = offsets.numel()
+    dev = raw.device
+    total_raw = 0
+    if n and (file is None or with_status):  # (sizes the file image and the ragged scratch)
+        total_raw = int(lengths.to(torch.int64).sum().item())
+    if max_len is None:
+        max_len = int(lengths.max().item()) if n else 0
+    if with_status:
+        max_len = max(0, min(int(max_len), 0xFFFFFFFF))
+    if file is None:
+        file = torch.zeros(max(1, file_offset + total_raw + 5 * n), dtype=torch.uint8, device=dev)
+    hoff = torch.empty(n, dtype=torch.int64, device=dev)
+    hsize = torch.empty(n, dtype=torch.int32, device=dev)
+    typ = torch.empty(n, dtype=torch.uint8, device=dev)
+    end = torch.empty(1, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev) if with_status else None
+    scratch = None
+    if compression in (1, 2) and n:
+        if with_status:  # (the zstd compressor's pool is part of it only for compression 2)
+            need = _lib.lvkv_sst_write_scratch_bytes_v2(n, total_raw,
+                                                        max_len if compression == 2 else 0)
+        else:
+            need = _lib.lvkv_sst_write_scratch_bytes(n, max_len)
+        scratch = torch.empty(int(need), dtype=torch.uint8, device=dev)
+    args = [_dev_ptr(raw, "raw", (torch.uint8, torch.int8)) if n else None,
+            _dev_ptr(offsets, "offsets", (torch.int64,)) if n else None,
+            _dev_ptr(lengths, "lengths", (torch.int32,), n) if n else None, n, compression,
+            int(zstd_level), max_len, _dev_ptr(scratch, "scratch") if scratch is not None else None,
+            _dev_ptr(file, "file", (torch.uint8, torch.int8)), file_offset,
+            _dev_ptr(hoff, "hoff") if n else None, _dev_ptr(hsize, "hsize") if n else None,
+            _dev_ptr(typ, "type") if n else None, _dev_ptr(end, "end")]
+    if with_status:
+        name = "lvkv_sst_write_blocks_status_device"
+        args += [scratch.numel() if scratch is not None else 0,
+                 _dev_ptr(status, "status") if n else None]
+    else:
+        name = "lvkv_sst_write_blocks_level_device"
+    with torch.cuda.device(dev):
+        rc = getattr(_lib, name)(*args, _stream_handle(stream, dev))
+    _check(name, rc)
+    return (file, hoff, hsize, typ, end) + ((status,) if with_status else ())
+
+
 def sst_write_blocks(raw, offsets, lengths, *, compression: int = 1, max_len: Optional[int] = None,
                      file=None, file_offset: int = 0, zstd_level: int = 1, stream=None):
     """Batched TableBuilder::WriteBlock + WriteRawBlock (table/table_builder.cc:
@@ -797,34 +845,8 @@ def sst_write_blocks(raw, offsets, lengths, *, compression: int = 1, max_len: Op
     from file_offset of the file image `file` (allocated when None: file_offset
     + sum(lengths + 5) bytes). Returns (file, handle offsets int64, handle
     sizes int32, types uint8, end offset int64 tensor of one)."""
-    torch = _torch()
-    n = offsets.numel()
-    dev = raw.device
-    if max_len is None:
-        max_len = int(lengths.max().item()) if n else 0
-    if file is None:
-        total = file_offset + (int(lengths.to(torch.int64).sum().item()) if n else 0) + 5 * n
-        file = torch.zeros(max(1, total), dtype=torch.uint8, device=dev)
-    hoff = torch.empty(n, dtype=torch.int64, device=dev)
-    hsize = torch.empty(n, dtype=torch.int32, device=dev)
-    typ = torch.empty(n, dtype=torch.uint8, device=dev)
-    end = torch.empty(1, dtype=torch.int64, device=dev)
-    scratch = None
-    if compression in (1, 2) and n:
-        scratch = torch.empty(int(_lib.lvkv_sst_write_scratch_bytes(n, max_len)),
-                              dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lvkv_sst_write_blocks_level_device(
-            _dev_ptr(raw, "raw", (torch.uint8, torch.int8)) if n else None,
-            _dev_ptr(offsets, "offsets", (torch.int64,)) if n else None,
-            _dev_ptr(lengths, "lengths", (torch.int32,), n) if n else None, n, compression,
-            int(zstd_level), max_len, _dev_ptr(scratch, "scratch") if scratch is not None else None,
-            _dev_ptr(file, "file", (torch.uint8, torch.int8)), file_offset,
-            _dev_ptr(hoff, "hoff") if n else None, _dev_ptr(hsize, "hsize") if n else None,
-            _dev_ptr(typ, "type") if n else None, _dev_ptr(end, "end"),
-            _stream_handle(stream, dev))
-    _check("lvkv_sst_write_blocks_level_device", rc)
-    return file, hoff, hsize, typ, end
+    return _sst_write(raw, offsets, lengths, compression, zstd_level, max_len, file, file_offset,
+                      stream, False)
 
 
 def sst_write_blocks_status(raw, offsets, lengths, *, compression: int = 1, zstd_level: int = 1,
@@ -839,39 +861,8 @@ def sst_write_blocks_status(raw, offsets, lengths, *, compression: int = 1, zstd
     with the bytes written, not with the block count times max_len. Returns
     (file, handle offsets int64, handle sizes int32, types uint8, end offset
     int64 tensor of one, status uint8)."""
-    torch = _torch()
-    n = offsets.numel()
-    dev = raw.device
-    total_raw = int(lengths.to(torch.int64).sum().item()) if n else 0
-    if max_len is None:
-        max_len = int(lengths.max().item()) if n else 0
-    max_len = max(0, min(int(max_len), 0xFFFFFFFF))
-    if file is None:
-        file = torch.zeros(max(1, file_offset + total_raw + 5 * n), dtype=torch.uint8, device=dev)
-    hoff = torch.empty(n, dtype=torch.int64, device=dev)
-    hsize = torch.empty(n, dtype=torch.int32, device=dev)
-    typ = torch.empty(n, dtype=torch.uint8, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    end = torch.empty(1, dtype=torch.int64, device=dev)
-    scratch = None
-    if compression in (1, 2) and n:
-        # (the zstd compressor's pool is part of it only for compression 2)
-        need = int(_lib.lvkv_sst_write_scratch_bytes_v2(n, total_raw,
-                                                        max_len if compression == 2 else 0))
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lvkv_sst_write_blocks_status_device(
-            _dev_ptr(raw, "raw", (torch.uint8, torch.int8)) if n else None,
-            _dev_ptr(offsets, "offsets", (torch.int64,)) if n else None,
-            _dev_ptr(lengths, "lengths", (torch.int32,), n) if n else None, n, compression,
-            int(zstd_level), max_len, _dev_ptr(scratch, "scratch") if scratch is not None else None,
-            _dev_ptr(file, "file", (torch.uint8, torch.int8)), file_offset,
-            _dev_ptr(hoff, "hoff") if n else None, _dev_ptr(hsize, "hsize") if n else None,
-            _dev_ptr(typ, "type") if n else None, _dev_ptr(end, "end"),
-            scratch.numel() if scratch is not None else 0,
-            _dev_ptr(status, "status") if n else None, _stream_handle(stream, dev))
-    _check("lvkv_sst_write_blocks_status_device", rc)
-    return file, hoff, hsize, typ, end, status
+    return _sst_write(raw, offsets, lengths, compression, zstd_level, max_len, file, file_offset,
+                      stream, True)
 
 
 def sst_read_blocks(file, handle_off, handle_size, *, max_ulen: int, verify: bool = True,

@@ -20,6 +20,7 @@
 #include "crc32c_uniform_common.h"
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
+#include "lvkv_launch.h"
 
 namespace lvkv {
 

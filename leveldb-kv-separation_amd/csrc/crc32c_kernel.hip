@@ -36,6 +36,7 @@
 
 #include "crc32c_device_common.h"
 #include "lvkv_kernel_args.h"
+#include "lvkv_launch.h"
 
 namespace lvkv {
 namespace {

@@ -11,6 +11,7 @@
 #include "crc32c_ragged_body.h"
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
+#include "lvkv_launch.h"
 
 namespace lvkv {
 namespace {
@@ -62,12 +63,6 @@ hipError_t launch_crc32c_ragged(const KernelArgs& a, const uint32_t* zpow,
   }
   return hipGetLastError();
 }
-
-hipError_t launch_crc32c_batch(const KernelArgs& args, bool uniform_aligned, int num_groups,
-                               hipStream_t stream);
-
-hipError_t launch_crc32c_long(const KernelArgs& args, const uint32_t* zpow,
-                              const uint32_t* lane_cols, int num_groups, hipStream_t stream);
 
 // General-layout batch (a.offsets set, a.row_tab = the device tables) on
 // `cus` CUs; a.nblocks is the launch's capacity when a.count is set. Blocks

@@ -27,6 +27,7 @@
 #include "crc32c_device_common.h"
 #include "crc32c_uniform_common.h"
 #include "lvkv_kernel_args.h"
+#include "lvkv_launch.h"
 
 namespace lvkv {
 namespace {

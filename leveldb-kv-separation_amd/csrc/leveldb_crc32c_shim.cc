@@ -12,9 +12,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-namespace lvkv {
-uint32_t cpu_crc32c_extend(uint32_t crc, const uint8_t* data, size_t n);
-}
+#include "lvkv_tables.h"
 
 namespace leveldb {
 namespace crc32c {

@@ -18,114 +18,11 @@
 
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
+#include "lvkv_launch.h"
 #include "lvkv_snappy.h"
 #include "lvkv_tables.h"
 
 namespace lvkv {
-
-hipError_t launch_crc32c_batch(const KernelArgs& args, bool uniform_aligned,
-                               int num_groups, hipStream_t stream);
-hipError_t launch_crc32c_general(const KernelArgs& a, int cus, hipStream_t stream);
-#ifdef LVKV_PROBE_BUILD
-extern uint64_t* g_log_stamps;
-extern uint64_t* g_asm_stamps;
-extern uint64_t* g_sst_stamps;
-extern uint32_t g_log_knobs;
-extern uint64_t* g_zstd_stamps;
-extern uint64_t* g_zstdc_stamps;
-hipError_t launch_crc32c_probe(const KernelArgs& args, int variant,
-                               int num_groups, hipStream_t stream);
-hipError_t launch_read_bw(const void* p, uint64_t bytes, uint32_t* out,
-                          int num_groups, hipStream_t stream);
-#endif
-hipError_t launch_crc32c_uniform(const UniformArgs& args, int variant,
-                                 int num_groups, hipStream_t stream);
-// Lane tables loaded first and written with the row tables (no end barrier),
-// chain A's loads issued before the row-table fill: the fastest schedule
-// measured (tools/probe.py v780; profiles/).
-constexpr int kSmallProductionVariant = 4 | 8;
-hipError_t launch_crc32c_uniform_small(const UniformArgs& args, int variant,
-                                       int num_groups, hipStream_t stream);
-hipError_t launch_crc32c_compact(const UniformArgs& args, int cfg, int num_groups,
-                                 hipStream_t stream);
-size_t log_gather_scratch_bytes(size_t capacity);
-hipError_t launch_log_gather(const uint8_t* file, const uint64_t* hdr_off, size_t capacity,
-                             const lvkv_log_report* phys, const lvkv_log_record* recs,
-                             uint32_t rec_cap, const lvkv_log_read_report* read, uint8_t* out,
-                             uint64_t out_cap, uint64_t* rec_pos, void* look, uint32_t tag,
-                             int cus, hipStream_t stream);
-hipError_t launch_sst_tables(const uint8_t* file, const uint64_t* toff, const uint64_t* tsize,
-                             uint64_t single_size, uint32_t ntables, uint64_t* d_off,
-                             uint32_t* d_size, uint32_t* d_actual, uint8_t* d_status,
-                             uint32_t capacity, lvkv_sst_report* reports, const FilterKey& fk,
-                             uint32_t gen, const KernelArgs& verify, const uint32_t* zpow,
-                             const uint32_t* lane_cols, int groups, int form,
-                             hipStream_t stream);
-hipError_t launch_log_blocks(const uint8_t* file, uint64_t size, uint64_t* hdr_off,
-                             uint32_t* actual, uint8_t* rec_status, uint32_t capacity,
-                             uint8_t* block_status, uint32_t* block_drop, lvkv_log_report* r,
-                             const uint32_t* zpow, const uint32_t* lane_cols, int cus,
-                             void* scratch, uint32_t* events, uint64_t* item_off,
-                             hipStream_t stream);
-size_t log_scratch_bytes(uint64_t size, uint32_t capacity, int cus);
-hipError_t launch_log_assemble(const uint32_t* events, const uint64_t* item_off,
-                               const uint64_t* hdr_off, const lvkv_log_report* phys,
-                               uint64_t size, uint32_t capacity, uint64_t initial_offset,
-                               lvkv_log_record* recs, uint32_t rec_cap,
-                               lvkv_log_corruption* reps, uint32_t rep_cap,
-                               lvkv_log_read_report* out, void* scratch, hipStream_t stream);
-size_t log_asm_scratch_bytes(size_t max_items);
-hipError_t launch_crc32c_long(const KernelArgs& args, const uint32_t* zpow,
-                              const uint32_t* lane_cols, int num_groups, hipStream_t stream);
-hipError_t launch_snappy_compress(const uint8_t* src, const uint64_t* src_off,
-                                  const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
-                                  uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
-                                  uint32_t max_len, hipStream_t stream);
-hipError_t launch_snappy_uncompress(const uint8_t* src, const uint64_t* src_off,
-                                    const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
-                                    const uint32_t* dst_cap, uint32_t* out_len, uint8_t* status,
-                                    uint32_t nblocks, uint32_t max_ulen, hipStream_t stream);
-uint64_t snappy_write_stride(uint32_t max_len);
-hipError_t launch_sst_write_blocks(const uint8_t* raw, const uint64_t* raw_off,
-                                   const uint32_t* raw_len, uint32_t nblocks, int compression,
-                                   uint32_t max_len, uint8_t* scratch, uint8_t* file,
-                                   uint64_t file_offset, uint64_t* hoff, uint32_t* hsize,
-                                   uint8_t* type, uint64_t* end, int zstd_level,
-                                   hipStream_t stream);
-hipError_t launch_zstd_compress(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len,
-                                uint8_t* dst, const uint64_t* dst_off, uint32_t* dst_len,
-                                uint8_t* status, uint32_t nblocks, uint32_t max_len, int level,
-                                uint64_t dst_stride, hipStream_t stream);
-size_t zstd_compress_big_scratch(uint32_t max_len);
-hipError_t launch_zstd_compress_big(const uint8_t* src, const uint64_t* src_off,
-                                    const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
-                                    uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
-                                    uint32_t max_len, int level, uint64_t dst_stride,
-                                    uint8_t* scratch, hipStream_t stream);
-uint64_t sst_write_v2_fixed(size_t nblocks, uint32_t max_len);
-uint64_t sst_write_v2_bytes(size_t nblocks, uint64_t total_raw, uint32_t max_len);
-hipError_t launch_sst_write_blocks_status(const uint8_t* raw, const uint64_t* raw_off,
-                                          const uint32_t* raw_len, uint32_t nblocks,
-                                          int compression, uint32_t max_len, uint8_t* scratch,
-                                          uint64_t scratch_bytes, uint8_t* file,
-                                          uint64_t file_offset, uint64_t* hoff, uint32_t* hsize,
-                                          uint8_t* type, uint64_t* end, int zstd_level,
-                                          uint8_t* status, hipStream_t stream);
-hipError_t launch_sst_read_blocks(const uint8_t* file, const uint64_t* hoff, const uint32_t* hsize,
-                                  uint32_t nblocks, uint8_t* out, const uint64_t* out_off,
-                                  const uint32_t* out_cap, uint32_t* out_len, uint8_t* status,
-                                  const uint8_t* vstatus, uint32_t max_ulen, hipStream_t stream);
-hipError_t launch_zstd_uncompress(const uint8_t* src, const uint64_t* src_off,
-                                  const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
-                                  const uint32_t* dst_cap, uint32_t* out_len, uint8_t* status,
-                                  uint32_t* detail, uint32_t nblocks, uint32_t max_ulen,
-                                  uint32_t block_mode, const uint8_t* vstatus, hipStream_t stream);
-int compact_capacity(int cfg);
-int compact_occupancy(int cfg);
-// 8 waves x 3 chains, two workgroups per CU, generated lane tables
-constexpr int kCompactProductionCfg = 9;
-uint32_t cpu_crc32c_extend(uint32_t crc, const uint8_t* data, size_t n);
-const char* cpu_crc32c_impl_name();
 
 namespace {
 
@@ -881,7 +778,7 @@ int lvkv_log_verify_device(const void* d_file, const uint64_t* d_hdr_offsets,
   return run_batch(a, nrecords, static_cast<hipStream_t>(stream));
 }
 
-size_t lvkv_snappy_max_compressed_length(size_t n) { return 32 + n + n / 6; }
+size_t lvkv_snappy_max_compressed_length(size_t n) { return snappy_bound(n); }
 
 int lvkv_snappy_compress_device(const void* d_src, const uint64_t* d_src_off,
                                 const uint32_t* d_src_len, void* d_dst,
@@ -938,9 +835,7 @@ size_t lvkv_sst_write_scratch_bytes(size_t nblocks, uint32_t max_len) {
   return nblocks * (snappy_write_stride(max_len) + 5);
 }
 
-size_t lvkv_zstd_compress_bound(size_t n) {
-  return n + (n >> 8) + (n < (size_t{128} << 10) ? ((size_t{128} << 10) - n) >> 11 : 0);
-}
+size_t lvkv_zstd_compress_bound(size_t n) { return zstd_bound(n); }
 
 int lvkv_zstd_compress_device(const void* d_src, const uint64_t* d_src_off,
                               const uint32_t* d_src_len, void* d_dst, const uint64_t* d_dst_off,
@@ -1000,9 +895,9 @@ int lvkv_sst_write_blocks_status_device(const void* d_raw, const uint64_t* d_raw
   if (nblocks == 0) {  // before every other check: d_end = file_offset, by the layout kernel
     int rc = LVKV_OK;
     if (current_ctx(&rc) == nullptr) return rc;
-    const hipError_t e = launch_sst_write_blocks(nullptr, nullptr, nullptr, 0, 0, 0, nullptr,
-                                                 nullptr, file_offset, nullptr, nullptr, nullptr,
-                                                 d_end, 1, static_cast<hipStream_t>(stream));
+    const hipError_t e = launch_sst_write_blocks(nullptr, nullptr, nullptr, 0, 0, 0, {}, nullptr,
+                                                 file_offset, nullptr, nullptr, nullptr, d_end, 1,
+                                                 nullptr, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? LVKV_OK : hip_fail(e);
   }
   if (compression < 0 || compression > 2) return LVKV_ERR_INVALID;
@@ -1016,9 +911,13 @@ int lvkv_sst_write_blocks_status_device(const void* d_raw, const uint64_t* d_raw
     return LVKV_ERR_INVALID;
   int rc = LVKV_OK;
   if (current_ctx(&rc) == nullptr) return rc;
-  const hipError_t e = launch_sst_write_blocks_status(
-      static_cast<const uint8_t*>(d_raw), d_raw_off, d_raw_len, static_cast<uint32_t>(nblocks),
-      compression, max_len, static_cast<uint8_t*>(d_scratch), scratch_bytes,
+  const uint32_t n = static_cast<uint32_t>(nblocks);
+  const SstWriteScratch scratch =
+      compression == 0 ? SstWriteScratch{}
+                       : sst_scratch_ragged(static_cast<uint8_t*>(d_scratch), scratch_bytes, n,
+                                            compression == 2 ? max_len : 0u);
+  const hipError_t e = launch_sst_write_blocks(
+      static_cast<const uint8_t*>(d_raw), d_raw_off, d_raw_len, n, compression, max_len, scratch,
       static_cast<uint8_t*>(d_file), file_offset, d_handle_off, d_handle_size, d_type, d_end,
       zstd_level, d_status, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e);
@@ -1052,9 +951,9 @@ int lvkv_sst_write_blocks_level_device(const void* d_raw, const uint64_t* d_raw_
   if (nblocks == 0) {  // d_end = file_offset, by the layout kernel (no host pointer kept)
     int rc = LVKV_OK;
     if (current_ctx(&rc) == nullptr) return rc;
-    const hipError_t e = launch_sst_write_blocks(nullptr, nullptr, nullptr, 0, compression, 0,
-                                                 nullptr, nullptr, file_offset, nullptr, nullptr,
-                                                 nullptr, d_end, zstd_level,
+    const hipError_t e = launch_sst_write_blocks(nullptr, nullptr, nullptr, 0, compression, 0, {},
+                                                 nullptr, file_offset, nullptr, nullptr, nullptr,
+                                                 d_end, zstd_level, nullptr,
                                                  static_cast<hipStream_t>(stream));
     return e == hipSuccess ? LVKV_OK : hip_fail(e);
   }
@@ -1064,10 +963,15 @@ int lvkv_sst_write_blocks_level_device(const void* d_raw, const uint64_t* d_raw_
   int rc = LVKV_OK;
   if (current_ctx(&rc) == nullptr) return rc;
   const hipStream_t hs = static_cast<hipStream_t>(stream);
+  const uint32_t n = static_cast<uint32_t>(nblocks);
+  const SstWriteScratch scratch =
+      compression == 0
+          ? SstWriteScratch{}
+          : sst_scratch_strided(static_cast<uint8_t*>(d_scratch), d_raw_len, n, max_len);
   hipError_t e = launch_sst_write_blocks(
-      static_cast<const uint8_t*>(d_raw), d_raw_off, d_raw_len, static_cast<uint32_t>(nblocks),
-      compression, max_len, static_cast<uint8_t*>(d_scratch), static_cast<uint8_t*>(d_file),
-      file_offset, d_handle_off, d_handle_size, d_type, d_end, zstd_level, hs);
+      static_cast<const uint8_t*>(d_raw), d_raw_off, d_raw_len, n, compression, max_len, scratch,
+      static_cast<uint8_t*>(d_file), file_offset, d_handle_off, d_handle_size, d_type, d_end,
+      zstd_level, nullptr, hs);
   if (e != hipSuccess) return hip_fail(e);
   // the trailers: Mask(CRC32C(contents + type)) by the batch CRC kernel
   return lvkv_sst_fill_trailers_device(d_file, d_handle_off, d_handle_size, nullptr, nblocks,

@@ -1,0 +1,182 @@
+// Everything that crosses a translation unit inside the library, declared
+// once: the kernel launchers (each defined beside its kernels), the
+// scratch-size functions their callers size buffers with, the production
+// kernel choices, and the two codec bounds. Every file that defines one of
+// these includes this header, so a signature that drifts fails to compile
+// instead of failing when the library is loaded.
+#ifndef LVKV_LAUNCH_H_
+#define LVKV_LAUNCH_H_
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "lvkv_crc32c.h"
+#include "lvkv_kernel_args.h"
+
+namespace lvkv {
+
+// ---- codec bounds -----------------------------------------------------------
+
+// ZSTD_compressBound (zstd.h, ZSTD_COMPRESSBOUND): the longest frame the
+// compressor writes for n bytes. In the caller's integer type.
+template <typename T>
+__host__ __device__ constexpr T zstd_bound(T n) {
+  return n + (n >> 8) + (n < (128u << 10) ? ((128u << 10) - n) >> 11 : 0u);
+}
+// snappy::MaxCompressedLength (snappy.cc): the longest stream for n bytes.
+template <typename T>
+__host__ __device__ constexpr T snappy_bound(T n) {
+  return 32u + n + n / 6u;
+}
+static_assert(zstd_bound(0u) == 64 && zstd_bound(4096u) == 4174, "ZSTD_compressBound");
+static_assert(zstd_bound(131071u) == 131582 && zstd_bound(131072u) == 131584, "ZSTD_compressBound");
+static_assert(snappy_bound(0u) == 32 && snappy_bound(4096u) == 4810, "snappy::MaxCompressedLength");
+
+// ---- batch CRC32C (crc32c_kernel.hip, crc32c_uniform.hip, crc32c_compact.hip,
+// crc32c_ragged.hip) ----------------------------------------------------------
+
+hipError_t launch_crc32c_batch(const KernelArgs& args, bool uniform_aligned, int num_groups,
+                               hipStream_t stream);
+hipError_t launch_crc32c_general(const KernelArgs& a, int cus, hipStream_t stream);
+int ragged_blocks_per_round(int cfg);
+hipError_t launch_crc32c_ragged(const KernelArgs& a, const uint32_t* zpow,
+                                const uint32_t* lane_cols, int cfg, int num_groups,
+                                hipStream_t stream);
+hipError_t launch_crc32c_long(const KernelArgs& args, const uint32_t* zpow,
+                              const uint32_t* lane_cols, int num_groups, hipStream_t stream);
+hipError_t launch_crc32c_uniform(const UniformArgs& args, int variant, int num_groups,
+                                 hipStream_t stream);
+// Lane tables loaded first and written with the row tables (no end barrier),
+// chain A's loads issued before the row-table fill: the fastest schedule
+// measured (tools/probe.py v780; profiles/).
+constexpr int kSmallProductionVariant = 4 | 8;
+hipError_t launch_crc32c_uniform_small(const UniformArgs& args, int variant, int num_groups,
+                                       hipStream_t stream);
+hipError_t launch_crc32c_compact(const UniformArgs& args, int cfg, int num_groups,
+                                 hipStream_t stream);
+int compact_capacity(int cfg);
+int compact_occupancy(int cfg);
+// 8 waves x 3 chains, two workgroups per CU, generated lane tables
+constexpr int kCompactProductionCfg = 9;
+
+// ---- whole-SSTable verify (lvkv_sst_table.hip) ------------------------------
+
+hipError_t launch_sst_tables(const uint8_t* file, const uint64_t* toff, const uint64_t* tsize,
+                             uint64_t single_size, uint32_t ntables, uint64_t* d_off,
+                             uint32_t* d_size, uint32_t* d_actual, uint8_t* d_status,
+                             uint32_t capacity, lvkv_sst_report* reports, const FilterKey& fk,
+                             uint32_t gen, const KernelArgs& verify, const uint32_t* zpow,
+                             const uint32_t* lane_cols, int groups, int form,
+                             hipStream_t stream);
+
+// ---- the WAL (lvkv_log_blocks.hip, lvkv_log_assemble.hip) -------------------
+
+size_t log_scratch_bytes(uint64_t size, uint32_t capacity, int cus);
+hipError_t launch_log_blocks(const uint8_t* file, uint64_t size, uint64_t* hdr_off,
+                             uint32_t* actual, uint8_t* rec_status, uint32_t capacity,
+                             uint8_t* block_status, uint32_t* block_drop, lvkv_log_report* r,
+                             const uint32_t* zpow, const uint32_t* lane_cols, int cus,
+                             void* scratch, uint32_t* events, uint64_t* item_off,
+                             hipStream_t stream);
+size_t log_asm_scratch_bytes(size_t max_items);
+hipError_t launch_log_assemble(const uint32_t* events, const uint64_t* item_off,
+                               const uint64_t* hdr_off, const lvkv_log_report* phys,
+                               uint64_t size, uint32_t capacity, uint64_t initial_offset,
+                               lvkv_log_record* recs, uint32_t rec_cap,
+                               lvkv_log_corruption* reps, uint32_t rep_cap,
+                               lvkv_log_read_report* out, void* scratch, hipStream_t stream);
+size_t log_gather_scratch_bytes(size_t capacity);
+hipError_t launch_log_gather(const uint8_t* file, const uint64_t* hdr_off, size_t capacity,
+                             const lvkv_log_report* phys, const lvkv_log_record* recs,
+                             uint32_t rec_cap, const lvkv_log_read_report* read, uint8_t* out,
+                             uint64_t out_cap, uint64_t* rec_pos, void* look, uint32_t tag,
+                             int cus, hipStream_t stream);
+
+// ---- block codecs (lvkv_snappy.hip, lvkv_zstd.hip, lvkv_zstd_compress.hip) --
+
+hipError_t launch_snappy_compress(const uint8_t* src, const uint64_t* src_off,
+                                  const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                  uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
+                                  uint32_t max_len, hipStream_t stream);
+hipError_t launch_snappy_uncompress(const uint8_t* src, const uint64_t* src_off,
+                                    const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                    const uint32_t* dst_cap, uint32_t* out_len, uint8_t* status,
+                                    uint32_t nblocks, uint32_t max_ulen, hipStream_t stream);
+hipError_t launch_zstd_compress(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len,
+                                uint8_t* dst, const uint64_t* dst_off, uint32_t* dst_len,
+                                uint8_t* status, uint32_t nblocks, uint32_t max_len, int level,
+                                uint64_t dst_stride, hipStream_t stream);
+size_t zstd_compress_big_scratch(uint32_t max_len);
+hipError_t launch_zstd_compress_big(const uint8_t* src, const uint64_t* src_off,
+                                    const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                    uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
+                                    uint32_t max_len, int level, uint64_t dst_stride,
+                                    uint8_t* scratch, hipStream_t stream);
+hipError_t launch_zstd_uncompress(const uint8_t* src, const uint64_t* src_off,
+                                  const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                  const uint32_t* dst_cap, uint32_t* out_len, uint8_t* status,
+                                  uint32_t* detail, uint32_t nblocks, uint32_t max_ulen,
+                                  uint32_t block_mode, const uint8_t* vstatus, hipStream_t stream);
+
+// ---- the block writer and reader (lvkv_snappy.hip) --------------------------
+
+// What a call of the writer works on besides the caller's arrays: where each
+// block's compressed form goes and the per-block arrays of the pipeline,
+// carved out of the caller's scratch by one of the two functions below (all
+// null for compression 0 and for an empty batch).
+struct SstWriteScratch {
+  uint8_t* slots;           // the compressed forms
+  uint64_t* slot_off;       // block b's at slots + slot_off[b]; nullptr: at b * stride
+  uint64_t stride;
+  uint64_t slot_cap;        // slot_off: the bytes the slots may take (their scan's bound)
+  const uint32_t* src_len;  // the lengths the compressor reads: raw_len, or the scan's
+  uint32_t* scan_len;       //   own (0 for a block without room), written by it
+  uint32_t* clen;           // compressed lengths
+  uint8_t* cst;             // the codec's verdicts
+  uint8_t* noroom;          // slot_off: 1 for a block whose slot did not fit
+  uint8_t* zstd_pool;       // slot_off: the zstd compressor's pool
+};
+// The fixed-stride contract, nblocks * (stride + 5) bytes
+// (lvkv_sst_write_scratch_bytes): the slots, then clen, then cst.
+uint64_t snappy_write_stride(uint32_t max_len);
+SstWriteScratch sst_scratch_strided(uint8_t* scratch, const uint32_t* raw_len, uint32_t nblocks,
+                                    uint32_t max_len);
+// The ragged contract (lvkv_sst_write_scratch_bytes_v2): up to 255 bytes of
+// alignment, 18 bytes a block (slot_off, scan_len, clen, cst, noroom), the
+// zstd pool (sized by pool_max_len: 0 without zstd), 16 spare bytes, then the
+// slots.
+uint64_t sst_write_v2_fixed(size_t nblocks, uint32_t max_len);
+uint64_t sst_write_v2_bytes(size_t nblocks, uint64_t total_raw, uint32_t max_len);
+SstWriteScratch sst_scratch_ragged(uint8_t* scratch, uint64_t scratch_bytes, uint32_t nblocks,
+                                   uint32_t pool_max_len);
+// status: the codec's verdict per block, or nullptr.
+hipError_t launch_sst_write_blocks(const uint8_t* raw, const uint64_t* raw_off,
+                                   const uint32_t* raw_len, uint32_t nblocks, int compression,
+                                   uint32_t max_len, const SstWriteScratch& s, uint8_t* file,
+                                   uint64_t file_offset, uint64_t* hoff, uint32_t* hsize,
+                                   uint8_t* type, uint64_t* end, int zstd_level, uint8_t* status,
+                                   hipStream_t stream);
+hipError_t launch_sst_read_blocks(const uint8_t* file, const uint64_t* hoff, const uint32_t* hsize,
+                                  uint32_t nblocks, uint8_t* out, const uint64_t* out_off,
+                                  const uint32_t* out_cap, uint32_t* out_len, uint8_t* status,
+                                  const uint8_t* vstatus, uint32_t max_ulen, hipStream_t stream);
+
+#ifdef LVKV_PROBE_BUILD
+// Probe builds (tools/probe/liblvkv_probe.so): timestamp buffers and knobs
+// set through lvkv_debug_*, the schedule-variant and read-bandwidth launchers.
+extern uint64_t* g_log_stamps;
+extern uint64_t* g_asm_stamps;
+extern uint64_t* g_sst_stamps;
+extern uint32_t g_log_knobs;
+extern uint64_t* g_zstd_stamps;
+extern uint64_t* g_zstdc_stamps;
+hipError_t launch_crc32c_probe(const KernelArgs& args, int variant, int num_groups,
+                               hipStream_t stream);
+hipError_t launch_read_bw(const void* p, uint64_t bytes, uint32_t* out, int num_groups,
+                          hipStream_t stream);
+#endif
+
+}  // namespace lvkv
+
+#endif  // LVKV_LAUNCH_H_

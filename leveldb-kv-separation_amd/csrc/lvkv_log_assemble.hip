@@ -43,6 +43,7 @@
 
 #include "crc32c_device_common.h"
 #include "lvkv_crc32c.h"
+#include "lvkv_launch.h"
 #include "lvkv_log_events.h"
 
 namespace lvkv {

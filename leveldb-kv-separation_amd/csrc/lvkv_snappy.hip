@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lvkv_launch.h"
 #include "lvkv_snappy.h"
 
 namespace lvkv {
@@ -48,7 +49,7 @@ struct ProbeOffsets {
 };
 __constant__ ProbeOffsets kProbe;
 
-__device__ __forceinline__ uint32_t table_size(uint32_t n) {
+__host__ __device__ __forceinline__ uint32_t table_size(uint32_t n) {
   uint32_t t = 256;
   while (t < kMaxTable && t < n) t <<= 1;
   return t;
@@ -359,11 +360,6 @@ struct UncompressArgs {
   const uint8_t* vstatus;
 };
 
-// snappy::MaxCompressedLength: the longest stream the decompressor stages.
-__host__ __device__ constexpr uint32_t snappy_in_cap(uint32_t out_cap) {
-  return 32u + out_cap + out_cap / 6u;
-}
-
 // The varint32 preamble at in[0, n): its value and size, or size 0 (bad).
 __device__ __forceinline__ uint32_t preamble(const uint8_t* in, uint32_t n, uint32_t* value) {
   uint32_t v = 0;
@@ -388,7 +384,7 @@ __global__ void __launch_bounds__(64) snappy_uncompress_kernel(UncompressArgs a)
   const uint8_t* src = a.src + a.src_off[b];
   // the staging area holds MaxCompressedLength(out_cap) bytes: every stream
   // a snappy encoder writes for out_cap bytes
-  const uint32_t in_cap = snappy_in_cap(a.out_cap);
+  const uint32_t in_cap = snappy_bound(a.out_cap);
   const uint32_t in_bytes = (in_cap + 16u + 15u) & ~15u;
   uint8_t* in = smem;
   uint8_t* out = smem + in_bytes;
@@ -656,6 +652,82 @@ __device__ __forceinline__ uint64_t shfl_up64(uint64_t v, uint32_t d) {
   return (static_cast<uint64_t>(hi) << 32) | lo;
 }
 
+// Exclusive scan of `local` over the workgroup's 1,024 threads: the sum of the
+// threads before this one, and in *total the sum of all. wsum: 17 u64 of LDS;
+// a barrier stands between a return and the next call (the caller's, after
+// its stores).
+__device__ __forceinline__ uint64_t block_scan(uint64_t local, uint64_t* wsum, uint64_t* total) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  uint64_t incl = local;
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint64_t y = shfl_up64(incl, d);
+    if (lane >= d) incl += y;
+  }
+  if (lane == 63) wsum[w] = incl;
+  __syncthreads();
+  if (w == 0) {
+    const uint64_t v = lane < 16 ? wsum[lane] : 0;
+    uint64_t s = v;
+    for (uint32_t d = 1; d < 16; d <<= 1) {
+      const uint64_t y = shfl_up64(s, d);
+      if (lane >= d) s += y;
+    }
+    if (lane < 16) wsum[lane] = s - v;  // exclusive
+    if (lane == 15) wsum[16] = s;       // the pass's total
+  }
+  __syncthreads();
+  *total = wsum[16];
+  return wsum[w] + incl - local;
+}
+
+// A block's slot for its compressed form: room for either codec's bound,
+// rounded to 16.
+__host__ __device__ constexpr uint64_t sst_slot_bytes(uint32_t n) {
+  const uint64_t sb = snappy_bound(uint64_t{n}), zb = zstd_bound(uint64_t{n});
+  return ((sb > zb ? sb : zb) + 15u) & ~uint64_t{15};
+}
+
+// Where each block's compressed form goes: an exclusive scan of the slots
+// from `first` (the bytes before it take what a block without room writes).
+// A block whose slot would end past `cap` has no room: it is compressed as
+// an empty block into the spare bytes at 0 and reported by sst_status_kernel.
+// One workgroup, a block a thread a pass.
+__global__ void __launch_bounds__(1024) sst_slots_kernel(const uint32_t* raw_len, uint32_t n,
+                                                         uint64_t first, uint64_t cap,
+                                                         uint64_t* off, uint32_t* elen,
+                                                         uint8_t* noroom) {
+  __shared__ uint64_t wsum[17];
+  uint64_t carry = first;
+  for (uint32_t base = 0; base < n; base += 1024) {
+    const uint32_t i = base + threadIdx.x;
+    const uint32_t L = i < n ? raw_len[i] : 0u;
+    const uint64_t local = i < n ? sst_slot_bytes(L) : 0u;
+    uint64_t total;
+    const uint64_t at = carry + block_scan(local, wsum, &total);
+    if (i < n) {
+      const bool room = at + local <= cap;
+      off[i] = room ? at : 0u;
+      elen[i] = room ? L : 0u;
+      noroom[i] = room ? 0 : 1;
+    }
+    carry += total;
+    __syncthreads();
+  }
+}
+
+// The verdict the caller sees, and the one the layout acts on.
+__global__ void __launch_bounds__(256) sst_status_kernel(uint8_t* cst, const uint8_t* noroom,
+                                                         uint32_t n, uint8_t* status) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  uint8_t st = LVKV_SNAPPY_OK;
+  if (cst != nullptr) {
+    st = noroom != nullptr && noroom[i] ? static_cast<uint8_t>(LVKV_SNAPPY_TOO_LARGE) : cst[i];
+    cst[i] = st;
+  }
+  status[i] = st;
+}
+
 // Which form each block keeps and where it lands: the compressed form when
 // it is smaller than raw - raw/8 (table_builder.cc:160-168), else raw with
 // type kNoCompression; handles are an exclusive scan of size + 5 (the
@@ -667,7 +739,7 @@ __global__ void __launch_bounds__(1024) sst_layout_kernel(const uint32_t* raw_le
                                                           uint8_t* type, uint64_t* end,
                                                           uint32_t ctype) {
   __shared__ uint64_t wsum[17];
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+  const uint32_t t = threadIdx.x;
   uint64_t carry = file_offset;
   for (uint32_t base = 0; base < n; base += 4096) {
     uint32_t sz[4];
@@ -685,25 +757,8 @@ __global__ void __launch_bounds__(1024) sst_layout_kernel(const uint32_t* raw_le
         local += sz[j] + 5u;
       }
     }
-    uint64_t incl = local;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint64_t y = shfl_up64(incl, d);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    if (w == 0) {
-      const uint64_t v = lane < 16 ? wsum[lane] : 0;
-      uint64_t s = v;
-      for (uint32_t d = 1; d < 16; d <<= 1) {
-        const uint64_t y = shfl_up64(s, d);
-        if (lane >= d) s += y;
-      }
-      if (lane < 16) wsum[lane] = s - v;  // exclusive
-      if (lane == 15) wsum[16] = s;       // the pass's total
-    }
-    __syncthreads();
-    uint64_t at = carry + wsum[w] + incl - local;
+    uint64_t total;
+    uint64_t at = carry + block_scan(local, wsum, &total);
     for (uint32_t j = 0; j < 4; ++j) {
       const uint32_t i = base + 4 * t + j;
       if (i < n) {
@@ -713,7 +768,7 @@ __global__ void __launch_bounds__(1024) sst_layout_kernel(const uint32_t* raw_le
         at += sz[j] + 5u;
       }
     }
-    carry += wsum[16];
+    carry += total;
     __syncthreads();
   }
   if (t == 0) *end = carry;
@@ -723,151 +778,28 @@ __global__ void __launch_bounds__(1024) sst_layout_kernel(const uint32_t* raw_le
 // contents at the handle, the type byte after them. The masked CRC is the
 // batch CRC kernel's (lvkv_sst_fill_trailers_device) over the same handles.
 __global__ void __launch_bounds__(256) sst_place_kernel(const uint8_t* raw, const uint64_t* raw_off,
-                                                        const uint8_t* comp, uint64_t comp_stride,
-                                                        const uint64_t* hoff, const uint32_t* hsize,
-                                                        const uint8_t* type, uint8_t* file) {
+                                                        const uint8_t* comp, const uint64_t* comp_off,
+                                                        uint64_t comp_stride, const uint64_t* hoff,
+                                                        const uint32_t* hsize, const uint8_t* type,
+                                                        uint8_t* file) {
   const uint32_t b = blockIdx.x, t = threadIdx.x;
   const uint32_t ty = type[b];
-  const uint8_t* src = ty ? comp + b * comp_stride : raw + raw_off[b];
+  const uint8_t* src =
+      ty ? comp + (comp_off ? comp_off[b] : b * comp_stride) : raw + raw_off[b];
   uint8_t* dst = file + hoff[b];
   const uint32_t n = hsize[b];
   for (uint32_t k = t; k < n; k += 256) dst[k] = src[k];
   if (t == 0) dst[n] = static_cast<uint8_t>(ty);
 }
 
-}  // namespace
-
-// A block's compressed scratch slot: room for either codec's bound
-// (snappy::MaxCompressedLength, ZSTD_compressBound).
-uint64_t snappy_write_stride(uint32_t max_len) {
-  const uint64_t zb = uint64_t{max_len} + (max_len >> 8) +
-                      (max_len < (128u << 10) ? ((128u << 10) - max_len) >> 11 : 0u);
-  const uint64_t sb = snappy_in_cap(max_len);
-  return ((sb > zb ? sb : zb) + 15u) & ~uint64_t{15};
-}
-
-hipError_t launch_zstd_compress(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len,
-                                uint8_t* dst, const uint64_t* dst_off, uint32_t* dst_len,
-                                uint8_t* status, uint32_t nblocks, uint32_t max_len, int level,
-                                uint64_t dst_stride, hipStream_t stream);
-
-hipError_t launch_sst_write_blocks(const uint8_t* raw, const uint64_t* raw_off,
-                                   const uint32_t* raw_len, uint32_t nblocks, int compression,
-                                   uint32_t max_len, uint8_t* scratch, uint8_t* file,
-                                   uint64_t file_offset, uint64_t* hoff, uint32_t* hsize,
-                                   uint8_t* type, uint64_t* end, int zstd_level,
-                                   hipStream_t stream) {
-  const uint64_t stride = snappy_write_stride(max_len);
-  uint32_t* clen = nullptr;
-  uint8_t* cst = nullptr;
-  if (compression == 1 && nblocks != 0) {
-    clen = reinterpret_cast<uint32_t*>(scratch + stride * nblocks);
-    cst = reinterpret_cast<uint8_t*>(clen + nblocks);
-    CompressArgs a{raw, raw_off, raw_len, scratch, nullptr, clen, cst, nblocks, 0, stride, max_len};
-    a.frag_cap = max(16u, min(max_len, kFrag));
-    const uint32_t in_bytes = (a.frag_cap + 16u + 15u) & ~15u;
-    uint32_t t = 256;
-    while (t < kMaxTable && t < a.frag_cap) t <<= 1;
-    const size_t lds = in_bytes + 1024u + 2u * t;
-    hipLaunchKernelGGL(snappy_compress_kernel, dim3(nblocks), dim3(64), lds, stream, a);
-  } else if (compression == 2 && nblocks != 0) {  // kZstdCompression
-    clen = reinterpret_cast<uint32_t*>(scratch + stride * nblocks);
-    cst = reinterpret_cast<uint8_t*>(clen + nblocks);
-    const hipError_t e = launch_zstd_compress(raw, raw_off, raw_len, scratch, nullptr, clen, cst,
-                                              nblocks, max_len, zstd_level, stride, stream);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(sst_layout_kernel, dim3(1), dim3(1024), 0, stream, raw_len, clen, cst,
-                     nblocks, file_offset, hoff, hsize, type, end,
-                     static_cast<uint32_t>(compression == 2 ? 2 : 1));
-  if (nblocks == 0) return hipGetLastError();  // (the layout stored end = file_offset)
-  hipLaunchKernelGGL(sst_place_kernel, dim3(nblocks), dim3(256), 0, stream, raw, raw_off,
-                     scratch, stride, hoff, hsize, type, file);
+// snappy_compress_kernel over a.nblocks blocks, a.frag_cap set: the LDS holds
+// a fragment of frag_cap bytes (16 of padding), the 256 slots of the literal
+// search and the hash table of that fragment.
+hipError_t run_snappy_compress(const CompressArgs& a, hipStream_t stream) {
+  const uint32_t in_bytes = (a.frag_cap + 16u + 15u) & ~15u;
+  const size_t lds = in_bytes + 1024u + 2u * table_size(a.frag_cap);
+  hipLaunchKernelGGL(snappy_compress_kernel, dim3(a.nblocks), dim3(64), lds, stream, a);
   return hipGetLastError();
-}
-
-// ---- the writer with ragged scratch and per-block status ----------------------
-
-namespace {
-
-// A block's slot in the ragged scratch: either codec's bound, rounded to 16.
-__host__ __device__ __forceinline__ uint64_t sst_slot_bytes(uint32_t n) {
-  const uint64_t zb = uint64_t{n} + (n >> 8) + (n < (128u << 10) ? ((128u << 10) - n) >> 11 : 0u);
-  const uint64_t sb = uint64_t{32} + n + n / 6u;
-  return ((sb > zb ? sb : zb) + 15u) & ~uint64_t{15};
-}
-
-// Where each block's compressed form goes: an exclusive scan of the slots
-// from `first` (the bytes before it take what a block without room writes).
-// A block whose slot would end past `cap` has no room: it is compressed as
-// an empty block into the spare bytes at 0 and reported by sst_status_kernel.
-// One workgroup, a block a thread a pass.
-__global__ void __launch_bounds__(1024) sst_slots_kernel(const uint32_t* raw_len, uint32_t n,
-                                                         uint64_t first, uint64_t cap,
-                                                         uint64_t* off, uint32_t* elen,
-                                                         uint8_t* noroom) {
-  __shared__ uint64_t wsum[17];
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  uint64_t carry = first;
-  for (uint32_t base = 0; base < n; base += 1024) {
-    const uint32_t i = base + t;
-    const uint32_t L = i < n ? raw_len[i] : 0u;
-    const uint64_t local = i < n ? sst_slot_bytes(L) : 0u;
-    uint64_t incl = local;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint64_t y = shfl_up64(incl, d);
-      if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    if (w == 0) {
-      const uint64_t v = lane < 16 ? wsum[lane] : 0;
-      uint64_t s = v;
-      for (uint32_t d = 1; d < 16; d <<= 1) {
-        const uint64_t y = shfl_up64(s, d);
-        if (lane >= d) s += y;
-      }
-      if (lane < 16) wsum[lane] = s - v;
-      if (lane == 15) wsum[16] = s;
-    }
-    __syncthreads();
-    const uint64_t at = carry + wsum[w] + incl - local;
-    if (i < n) {
-      const bool room = at + local <= cap;
-      off[i] = room ? at : 0u;
-      elen[i] = room ? L : 0u;
-      noroom[i] = room ? 0 : 1;
-    }
-    carry += wsum[16];
-    __syncthreads();
-  }
-}
-
-// The verdict the caller sees, and the one the layout acts on.
-__global__ void __launch_bounds__(256) sst_status_kernel(uint8_t* cst, const uint8_t* noroom,
-                                                         uint32_t n, uint8_t* status) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  uint8_t st = LVKV_SNAPPY_OK;
-  if (cst != nullptr) {
-    st = noroom[i] ? static_cast<uint8_t>(LVKV_SNAPPY_TOO_LARGE) : cst[i];
-    cst[i] = st;
-  }
-  status[i] = st;
-}
-
-// sst_place_kernel with each block's own scratch offset.
-__global__ void __launch_bounds__(256) sst_place_ragged_kernel(const uint8_t* raw, const uint64_t* raw_off,
-                                                               const uint8_t* comp, const uint64_t* comp_off,
-                                                               const uint64_t* hoff, const uint32_t* hsize,
-                                                               const uint8_t* type, uint8_t* file) {
-  const uint32_t b = blockIdx.x, t = threadIdx.x;
-  const uint32_t ty = type[b];
-  const uint8_t* src = ty ? comp + comp_off[b] : raw + raw_off[b];
-  uint8_t* dst = file + hoff[b];
-  const uint32_t n = hsize[b];
-  for (uint32_t k = t; k < n; k += 256) dst[k] = src[k];
-  if (t == 0) dst[n] = static_cast<uint8_t>(ty);
 }
 
 constexpr uint64_t kSstSpare = 16;  // the slot of the blocks without room
@@ -876,73 +808,92 @@ uint64_t sst_v2_head(size_t nblocks) {  // off u64, elen u32, clen u32, cst u8, 
   return (uint64_t{nblocks} * 18u + 255u) & ~uint64_t{255};
 }
 
+uint64_t sst_v2_pool(uint32_t max_len) {  // the zstd compressor's, 0 up to 20,480
+  return (zstd_compress_big_scratch(max_len) + 255u) & ~uint64_t{255};
+}
+
 }  // namespace
 
-size_t zstd_compress_big_scratch(uint32_t max_len);
-hipError_t launch_zstd_compress_big(const uint8_t* src, const uint64_t* src_off,
-                                    const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
-                                    uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
-                                    uint32_t max_len, int level, uint64_t dst_stride,
-                                    uint8_t* scratch, hipStream_t stream);
+uint64_t snappy_write_stride(uint32_t max_len) { return sst_slot_bytes(max_len); }
+
+SstWriteScratch sst_scratch_strided(uint8_t* scratch, const uint32_t* raw_len, uint32_t nblocks,
+                                    uint32_t max_len) {
+  SstWriteScratch s{};
+  s.slots = scratch;
+  s.stride = snappy_write_stride(max_len);
+  s.src_len = raw_len;
+  s.clen = reinterpret_cast<uint32_t*>(scratch + s.stride * nblocks);
+  s.cst = reinterpret_cast<uint8_t*>(s.clen + nblocks);
+  return s;
+}
 
 // The part of the v2 scratch that does not hold compressed blocks: alignment
 // slack, the per-block arrays, the zstd compressor's pool.
 uint64_t sst_write_v2_fixed(size_t nblocks, uint32_t max_len) {
-  return 256u + sst_v2_head(nblocks) + ((zstd_compress_big_scratch(max_len) + 255u) & ~uint64_t{255});
+  return 256u + sst_v2_head(nblocks) + sst_v2_pool(max_len);
 }
 
 uint64_t sst_write_v2_bytes(size_t nblocks, uint64_t total_raw, uint32_t max_len) {
-  // sum of slots <= total + total / 6 + 79 a block (either bound + rounding)
-  return sst_write_v2_fixed(nblocks, max_len) + kSstSpare + total_raw + total_raw / 6u +
+  // sum of slots <= total + total / 6 (MaxCompressedLength less its constant)
+  // + 79 a block (either bound's constant + rounding)
+  return sst_write_v2_fixed(nblocks, max_len) + kSstSpare + (snappy_bound(total_raw) - 32u) +
          uint64_t{nblocks} * 80u;
 }
 
-hipError_t launch_sst_write_blocks_status(const uint8_t* raw, const uint64_t* raw_off,
-                                          const uint32_t* raw_len, uint32_t nblocks,
-                                          int compression, uint32_t max_len, uint8_t* scratch,
-                                          uint64_t scratch_bytes, uint8_t* file,
-                                          uint64_t file_offset, uint64_t* hoff, uint32_t* hsize,
-                                          uint8_t* type, uint64_t* end, int zstd_level,
-                                          uint8_t* status, hipStream_t stream) {
-  uint32_t* clen = nullptr;
-  uint8_t *cst = nullptr, *noroom = nullptr, *area = nullptr;
-  uint64_t* off = nullptr;
-  if (compression != 0) {
-    uint8_t* base = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(scratch) + 255u) &
-                                               ~uintptr_t{255});
-    const uint64_t slack = static_cast<uint64_t>(base - scratch);
-    off = reinterpret_cast<uint64_t*>(base);
-    uint32_t* elen = reinterpret_cast<uint32_t*>(off + nblocks);
-    clen = elen + nblocks;
-    cst = reinterpret_cast<uint8_t*>(clen + nblocks);
-    noroom = cst + nblocks;
-    uint8_t* zs = base + sst_v2_head(nblocks);
-    const uint64_t zbytes =
-        compression == 2 ? (zstd_compress_big_scratch(max_len) + 255u) & ~uint64_t{255} : 0u;
-    area = zs + zbytes;
-    const uint64_t used = slack + sst_v2_head(nblocks) + zbytes;  // (the caller checked: <= bytes - spare)
-    hipLaunchKernelGGL(sst_slots_kernel, dim3(1), dim3(1024), 0, stream, raw_len, nblocks,
-                       kSstSpare, scratch_bytes - used, off, elen, noroom);
+SstWriteScratch sst_scratch_ragged(uint8_t* scratch, uint64_t scratch_bytes, uint32_t nblocks,
+                                   uint32_t pool_max_len) {
+  SstWriteScratch s{};
+  uint8_t* base = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(scratch) + 255u) &
+                                             ~uintptr_t{255});
+  s.slot_off = reinterpret_cast<uint64_t*>(base);
+  s.scan_len = reinterpret_cast<uint32_t*>(s.slot_off + nblocks);
+  s.src_len = s.scan_len;
+  s.clen = s.scan_len + nblocks;
+  s.cst = reinterpret_cast<uint8_t*>(s.clen + nblocks);
+  s.noroom = s.cst + nblocks;
+  s.zstd_pool = base + sst_v2_head(nblocks);
+  s.slots = s.zstd_pool + sst_v2_pool(pool_max_len);
+  // (the caller checked: the slots start at least kSstSpare before the end)
+  s.slot_cap = scratch_bytes - static_cast<uint64_t>(s.slots - scratch);
+  return s;
+}
+
+// The pipeline: the slots scan (where the scratch has per-block offsets), the
+// codec, the status merge (where a status is asked for), the layout, the
+// place. An empty batch runs the layout alone, which stores end = file_offset.
+hipError_t launch_sst_write_blocks(const uint8_t* raw, const uint64_t* raw_off,
+                                   const uint32_t* raw_len, uint32_t nblocks, int compression,
+                                   uint32_t max_len, const SstWriteScratch& s, uint8_t* file,
+                                   uint64_t file_offset, uint64_t* hoff, uint32_t* hsize,
+                                   uint8_t* type, uint64_t* end, int zstd_level, uint8_t* status,
+                                   hipStream_t stream) {
+  const bool any = nblocks != 0;
+  if (any && compression != 0) {
+    if (s.slot_off != nullptr)
+      hipLaunchKernelGGL(sst_slots_kernel, dim3(1), dim3(1024), 0, stream, raw_len, nblocks,
+                         kSstSpare, s.slot_cap, s.slot_off, s.scan_len, s.noroom);
+    hipError_t e;
     if (compression == 1) {
-      CompressArgs a{raw, raw_off, elen, area, off, clen, cst, nblocks, kFrag};
-      const uint32_t in_bytes = (kFrag + 16u + 15u) & ~15u;
-      uint32_t t = 256;
-      while (t < kMaxTable && t < kFrag) t <<= 1;
-      const size_t lds = in_bytes + 1024u + 2u * t;
-      hipLaunchKernelGGL(snappy_compress_kernel, dim3(nblocks), dim3(64), lds, stream, a);
-    } else {
-      const hipError_t e = launch_zstd_compress_big(raw, raw_off, elen, area, off, clen, cst,
-                                                    nblocks, max_len, zstd_level, 0, zs, stream);
-      if (e != hipSuccess) return e;
+      // a stride was sized from max_len; a slot of its own holds any block's bound
+      const uint32_t frag_cap = s.slot_off != nullptr ? kFrag : max(16u, min(max_len, kFrag));
+      e = run_snappy_compress(CompressArgs{raw, raw_off, s.src_len, s.slots, s.slot_off, s.clen,
+                                           s.cst, nblocks, frag_cap, s.stride, max_len},
+                              stream);
+    } else {  // kZstdCompression (one kernel when max_len <= 20,480)
+      e = launch_zstd_compress_big(raw, raw_off, s.src_len, s.slots, s.slot_off, s.clen, s.cst,
+                                   nblocks, max_len, zstd_level, s.stride, s.zstd_pool, stream);
     }
+    if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(sst_status_kernel, dim3((nblocks + 255u) / 256u), dim3(256), 0, stream, cst,
-                     noroom, nblocks, status);
-  hipLaunchKernelGGL(sst_layout_kernel, dim3(1), dim3(1024), 0, stream, raw_len, clen, cst,
+  if (any && status != nullptr)
+    hipLaunchKernelGGL(sst_status_kernel, dim3((nblocks + 255u) / 256u), dim3(256), 0, stream,
+                       s.cst, s.noroom, nblocks, status);
+  hipLaunchKernelGGL(sst_layout_kernel, dim3(1), dim3(1024), 0, stream, raw_len, s.clen, s.cst,
                      nblocks, file_offset, hoff, hsize, type, end,
                      static_cast<uint32_t>(compression == 2 ? 2 : 1));
-  hipLaunchKernelGGL(sst_place_ragged_kernel, dim3(nblocks), dim3(256), 0, stream, raw, raw_off,
-                     area, off, hoff, hsize, type, file);
+  if (any)
+    hipLaunchKernelGGL(sst_place_kernel, dim3(nblocks), dim3(256), 0, stream, raw, raw_off,
+                       s.slots, s.slot_off, s.stride, hoff, hsize, type, file);
   return hipGetLastError();
 }
 
@@ -953,7 +904,7 @@ hipError_t launch_sst_read_blocks(const uint8_t* file, const uint64_t* hoff, con
   UncompressArgs a{file, hoff, hsize, out, out_off, out_cap, out_len, status, nblocks, 0, 1,
                    vstatus};
   a.out_cap = max(16u, max_ulen);
-  const size_t lds = ((snappy_in_cap(a.out_cap) + 16u + 15u) & ~15u) + ((a.out_cap + 15u) & ~15u);
+  const size_t lds = ((snappy_bound(a.out_cap) + 16u + 15u) & ~15u) + ((a.out_cap + 15u) & ~15u);
   hipLaunchKernelGGL(snappy_uncompress_kernel, dim3(nblocks), dim3(64), lds, stream, a);
   hipLaunchKernelGGL(snappy_uncompress_big_kernel, dim3((nblocks + kBigChunk - 1u) / kBigChunk),
                      dim3(64), kBigWin + 16u + kBigRing, stream, a);
@@ -964,14 +915,9 @@ hipError_t launch_snappy_compress(const uint8_t* src, const uint64_t* src_off,
                                   const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
                                   uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
                                   uint32_t max_len, hipStream_t stream) {
-  CompressArgs a{src, src_off, src_len, dst, dst_off, dst_len, status, nblocks, 0};
-  a.frag_cap = max(16u, min(max_len, kFrag));
-  const uint32_t in_bytes = (a.frag_cap + 16u + 15u) & ~15u;
-  uint32_t t = 256;
-  while (t < kMaxTable && t < a.frag_cap) t <<= 1;
-  const size_t lds = in_bytes + 1024u + 2u * t;
-  hipLaunchKernelGGL(snappy_compress_kernel, dim3(nblocks), dim3(64), lds, stream, a);
-  return hipGetLastError();
+  const uint32_t frag_cap = max(16u, min(max_len, kFrag));
+  return run_snappy_compress(
+      CompressArgs{src, src_off, src_len, dst, dst_off, dst_len, status, nblocks, frag_cap}, stream);
 }
 
 hipError_t launch_snappy_uncompress(const uint8_t* src, const uint64_t* src_off,
@@ -981,7 +927,7 @@ hipError_t launch_snappy_uncompress(const uint8_t* src, const uint64_t* src_off,
   UncompressArgs a{src, src_off, src_len, dst, dst_off, dst_cap, out_len, status, nblocks, 0};
   a.out_cap = dst_cap == nullptr ? 0u : max(16u, max_ulen);
   const size_t lds = dst_cap == nullptr ? 16u
-                                        : ((snappy_in_cap(a.out_cap) + 16u + 15u) & ~15u) +
+                                        : ((snappy_bound(a.out_cap) + 16u + 15u) & ~15u) +
                                               ((a.out_cap + 15u) & ~15u);
   hipLaunchKernelGGL(snappy_uncompress_kernel, dim3(nblocks), dim3(64), lds, stream, a);
   if (dst_cap != nullptr)  // (the blocks past the LDS staging, any size)

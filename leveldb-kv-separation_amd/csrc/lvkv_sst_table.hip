@@ -53,6 +53,7 @@
 #include "crc32c_ragged_body.h"
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
+#include "lvkv_launch.h"
 
 namespace lvkv {
 
@@ -1230,8 +1231,6 @@ __global__ void __launch_bounds__(64 * kFW, 4)
 }
 
 }  // namespace
-
-hipError_t launch_crc32c_general(const KernelArgs& a, int cus, hipStream_t stream);
 
 #ifdef LVKV_PROBE_BUILD
 uint64_t* g_sst_stamps = nullptr;  // lvkv_debug_sst_stamps

@@ -38,6 +38,10 @@ void build_zpow_tables(uint32_t* zpow);
 //   register xors instead of dependent table lookups (group_crc)
 void build_zmul_columns(uint32_t* zmul);
 
+// The per-call host CRC32C (lvkv_cpu_crc32c.cpp) and the name of the
+// implementation it picked.
+uint32_t cpu_crc32c_extend(uint32_t crc, const uint8_t* data, size_t n);
+const char* cpu_crc32c_impl_name();
 
 }  // namespace lvkv
 

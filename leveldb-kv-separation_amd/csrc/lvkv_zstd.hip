@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lvkv_launch.h"
 #include "lvkv_snappy.h"
 #include "lvkv_zstd_tables.h"
 
@@ -360,15 +361,11 @@ struct Lds {
 
 constexpr uint32_t kHufEntries = 2048, kFseLL = 512, kFseOF = 256, kFseML = 512, kFseW = 64;
 
-__host__ __device__ constexpr uint32_t zstd_in_cap(uint32_t out_cap) {
-  // ZSTD_compressBound(out_cap) (1.4.9): every frame the library writes
-  return out_cap + (out_cap >> 8) + (out_cap < (128u << 10) ? ((128u << 10) - out_cap) >> 11 : 0u);
-}
 __host__ __device__ constexpr uint32_t round16(uint32_t x) { return (x + 15u) & ~15u; }
 constexpr uint32_t kTabBytes =
     2u * kHufEntries + 128u + 2u * (kFseLL + kFseOF + kFseML + kFseW) + 512u + 512u + 512u;
 __host__ __device__ constexpr uint32_t zstd_lds_bytes(uint32_t out_cap) {
-  return round16(zstd_in_cap(out_cap) + 16u + 4u) + round16(out_cap) + kTabBytes;
+  return round16(zstd_bound(out_cap) + 16u + 4u) + round16(out_cap) + kTabBytes;
 }
 // The HBM-output kernel's input window: a compressed block (< 128 KiB) from
 // any 4-aligned start, + slack for the register-window reads past its end.
@@ -1258,11 +1255,11 @@ __device__ __forceinline__ void zstd_stream(const ZArgs& a, uint32_t b, uint8_t*
                                  : finish(kOK, static_cast<uint32_t>(csize), kFOk);
   const uint32_t cap = uni(a.dst_cap[b]);
   if (csize > cap) return finish(kCap, csize > 0xFFFFFFFFull ? 0xFFFFFFFFu : csize, kFOk);
-  if (!Global && (csize > a.out_cap || n > zstd_in_cap(a.out_cap)))
+  if (!Global && (csize > a.out_cap || n > zstd_bound(a.out_cap)))
     return finish(kBig, csize, kFOk);
   uint8_t* const dst = a.dst + a.dst_off[b];
   Lds L = Global ? lds_layout(smem, kZWinBytes, 0)
-                 : lds_layout(smem, round16(zstd_in_cap(a.out_cap) + 16u + 4u), round16(a.out_cap));
+                 : lds_layout(smem, round16(zstd_bound(a.out_cap) + 16u + 4u), round16(a.out_cap));
   uint8_t* const win = L.in;
   if (Global) L.out = dst;
   uint64_t* stamp = a.stamps != nullptr ? a.stamps + 16u * b : nullptr;

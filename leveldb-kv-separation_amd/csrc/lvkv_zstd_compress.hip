@@ -36,6 +36,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lvkv_launch.h"
 #include "lvkv_zstd.h"
 
 namespace lvkv {

@@ -248,7 +248,7 @@ def test_device_codec_empty_batch(lvkv, gpu):
     assert dl.numel() == 0 and st.numel() == 0
     _, _, dl, st = lvkv.snappy_uncompress(z8, e64, e32, max_ulen=4096)
     assert dl.numel() == 0 and st.numel() == 0
-    for comp in (0, 1):  # no blocks: Rep::offset stays where it was
+    for comp in (0, 1, 2):  # no blocks: Rep::offset stays where it was
         _, _, _, _, end = lvkv.sst_write_blocks(z8, e64, e32, compression=comp,
                                                 file_offset=987654321)
         torch.cuda.synchronize()
@@ -324,6 +324,26 @@ def test_device_write_blocks_longer_than_max_len_stay_raw(lvkv, gpu):
     torch.cuda.synchronize()
     types = typ.cpu().tolist()
     assert types[1] == 0 and types[0] == types[2] == types[3] == 1
+    img = file.cpu().numpy().tobytes()
+    for raw, o, s in zip(raws, hoff.cpu().tolist(), hsize.cpu().tolist()):
+        assert so.read_block(img, o, s) == (so.READ_OK, raw)
+    assert int(end.item()) == sum(hsize.cpu().tolist()) + 5 * len(raws)
+
+
+@pytest.mark.gpu
+def test_device_write_blocks_zstd_longer_than_max_len_stay_raw(lvkv, gpu):
+    """The same with kZstdCompression: a block one byte past max_len is
+    TOO_LARGE for the compressor and stays raw, one of exactly max_len is
+    compressed. Every block reads back to its bytes."""
+    import torch
+    from tools.db_bench_data import block_batch
+    bench = block_batch(4).tobytes()
+    raws = [bench[:4096], bench[7:7 + 4097], bench[100:200]]
+    src, off, ln = _pack(torch, gpu, raws, skew=1)
+    file, hoff, hsize, typ, end = lvkv.sst_write_blocks(src, off, ln, compression=2,
+                                                        zstd_level=1, max_len=4096)
+    torch.cuda.synchronize()
+    assert typ.cpu().tolist() == [2, 0, 2]
     img = file.cpu().numpy().tobytes()
     for raw, o, s in zip(raws, hoff.cpu().tolist(), hsize.cpu().tolist()):
         assert so.read_block(img, o, s) == (so.READ_OK, raw)

@@ -344,3 +344,57 @@ def test_scratch_too_small_for_a_block_is_reported(lvkv, gpu):
     assert st.cpu().tolist()[1] == lvkv.ZSTD_TOO_LARGE and typ.cpu().tolist()[1] == 0
     assert (scratch[need:] == 0xAB).all().item()
     _read_back(lvkv, torch, gpu, file, hoff, hsize, raws)
+
+
+N_PASSES = 4101  # past the slots scan's pass (1,024 blocks) and the layout scan's (4,096)
+
+
+@functools.lru_cache(maxsize=1)
+def _many_small_raws():
+    """4,101 blocks of 0-96 bytes: odd indices random bytes (kept raw), even
+    ones a repeated byte (compressed)."""
+    rng = np.random.default_rng(4101)
+    out = []
+    for k in range(N_PASSES):
+        n = int(rng.integers(0, 97))
+        if k % 2:
+            out.append(rng.integers(0, 256, n, dtype=np.uint8).tobytes())
+        else:
+            out.append(bytes([int(rng.integers(0, 256))]) * n)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _many_small_image(compression):
+    return so.write_blocks(_many_small_raws(), compression, 123, zstd_level=1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("compression", [0, 1, 2])
+@pytest.mark.parametrize("with_status", [False, True])
+def test_writer_image_across_scan_passes(lvkv, gpu, with_status, compression):
+    """Both writers on a batch that takes the slots scan through five passes
+    and the layout scan through two: the carry from pass to pass puts every
+    handle where WriteBlock does, for raw and compressed blocks on both sides
+    of both boundaries."""
+    import torch
+    raws = _many_small_raws()
+    img, handles, types = _many_small_image(compression)
+    if compression:
+        for lo, hi in [(0, 1024), (1024, 4096), (4096, N_PASSES)]:
+            assert set(types[lo:hi]) == {0, compression}
+    src, off, ln = _pack(torch, gpu, raws, skew=1)
+    if with_status:
+        file, hoff, hsize, typ, end, st = lvkv.sst_write_blocks_status(
+            src, off, ln, compression=compression, zstd_level=1, file_offset=123)
+    else:
+        file, hoff, hsize, typ, end = lvkv.sst_write_blocks(
+            src, off, ln, compression=compression, zstd_level=1, file_offset=123)
+    torch.cuda.synchronize()
+    if with_status:
+        assert st.cpu().tolist() == [lvkv.ZSTD_OK] * len(raws)
+    assert typ.cpu().tolist() == types
+    assert hoff.cpu().tolist() == [h[0] for h in handles]
+    assert hsize.cpu().tolist() == [h[1] for h in handles]
+    assert int(end.item()) == 123 + len(img)
+    assert file.cpu().numpy()[123:123 + len(img)].tobytes() == img

@@ -35,13 +35,15 @@ def main():
     src = torch.from_numpy(block_batch(nb, L)).to(dev)
     off = torch.arange(nb, dtype=torch.int64, device=dev) * L
     ln = torch.full((nb,), L, dtype=torch.int32, device=dev)
-    zb = L + (L >> 8) + ((131072 - L) >> 11)
+    lib = ctypes.CDLL(str(libpath))
+    lib.lvkv_zstd_compress_bound.argtypes = [ctypes.c_size_t]
+    lib.lvkv_zstd_compress_bound.restype = ctypes.c_size_t
+    zb = lib.lvkv_zstd_compress_bound(L)
     dst = torch.empty(nb * zb, dtype=torch.uint8, device=dev)
     doff = torch.arange(nb, dtype=torch.int64, device=dev) * zb
     dl = torch.empty(nb, dtype=torch.int32, device=dev)
     st = torch.empty(nb, dtype=torch.uint8, device=dev)
     stamps = torch.zeros(nb * 16, dtype=torch.int64, device=dev)
-    lib = ctypes.CDLL(str(libpath))
     vp = ctypes.c_void_p
     has_stamps = hasattr(lib, "lvkv_debug_zstdc_stamps")
     if has_stamps:

@@ -12,18 +12,7 @@
 
 #include <vector>
 
-namespace lvkv {
-hipError_t launch_zstd_compress(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len,
-                                uint8_t* dst, const uint64_t* dst_off, uint32_t* dst_len,
-                                uint8_t* status, uint32_t nblocks, uint32_t max_len, int level,
-                                uint64_t dst_stride, hipStream_t stream);
-size_t zstd_compress_big_scratch(uint32_t max_len);
-hipError_t launch_zstd_compress_big(const uint8_t* src, const uint64_t* src_off,
-                                    const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
-                                    uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
-                                    uint32_t max_len, int level, uint64_t dst_stride,
-                                    uint8_t* scratch, hipStream_t stream);
-}
+#include "lvkv_launch.h"
 
 static std::vector<uint8_t> slurp(const char* p) {
   FILE* f = fopen(p, "rb");
@@ -50,7 +39,7 @@ int main(int argc, char** argv) {
     off[i] = p;
     doff[i] = q;
     p += len[i];
-    q += len[i] + (len[i] >> 8) + (len[i] < 131072 ? (131072 - len[i]) >> 11 : 0) + 16;
+    q += lvkv::zstd_bound(len[i]) + 16;
   }
   in.resize(p + 64);
   std::vector<uint8_t> dst(q + 64), st(n);

@@ -282,7 +282,7 @@ def main():
             res["cpu_libzstd_1_4_9"] = zcpu
     # zstd compress (port::Zstd_Compress at level 1, LevelDB's default): the
     # device compressor over the nb blocks, one launch
-    zb = L + (L >> 8) + ((131072 - L) >> 11)
+    zb = lvkv.zstd_compress_bound(L)
     zdst = torch.empty(nb * zb, dtype=torch.uint8, device=dev)
     zdoff = torch.arange(nb, dtype=torch.int64, device=dev) * zb
     zlen, zst = torch.empty_like(dlen), torch.empty_like(st)
