@@ -28,12 +28,6 @@ from conftest import GOLDEN, REPO
 BIG = 131072
 
 
-@functools.lru_cache(maxsize=None)
-def _frame(x: bytes, level: int) -> bytes:
-    """The oracle's frame, computed once per (block, level) for all tests."""
-    return ze.compress(x, level)
-
-
 # ---- CPU -----------------------------------------------------------------------
 
 def test_oracle_matches_library_on_large_blocks():
@@ -46,7 +40,7 @@ def test_oracle_matches_library_on_large_blocks():
         x = blocks[r["name"]]
         assert len(x) == r["input_len"] and hashlib.sha256(x).hexdigest() == r["input_sha256"], \
             f"{r['name']}: the input rebuilt from its seed is not the pinned one"
-        f = _frame(x, r["level"])
+        f = zb.frame(x, r["level"])
         if len(f) != r["frame_len"] or hashlib.sha256(f).hexdigest() != r["frame_sha256"]:
             bad.append((r["name"], r["level"]))
     assert not bad, f"oracle differs from libzstd 1.4.9 on {bad}"
@@ -83,18 +77,41 @@ def test_validation_without_a_device_call(lvkv):
     assert z(20481, None, 0) == lvkv.LVKV_ERR_INVALID
 
 
-def test_emulated_kernel_on_edge_blocks():
+@pytest.fixture(scope="module")
+def emu():
+    """The kernels compiled for the CPU, once for the tests that run them."""
+    r = subprocess.run(["bash", str(REPO / "tools/simt_emu/emu_build.sh")], capture_output=True,
+                       text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+
+def test_emulated_kernel_on_edge_blocks(emu):
     """The kernels compiled for the CPU (tools/simt_emu: 64 threads a wave,
     AddressSanitizer and UBSan, the scratch and the input allocated exactly)
     on three edge blocks: a match and a literal run past 65,535, and the
     first size the second kernel takes."""
-    r = subprocess.run(["bash", str(REPO / "tools/simt_emu/emu_build.sh")], capture_output=True,
-                       text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([sys.executable, str(REPO / "tools/simt_emu/zstdc_check.py"), "big",
                         "long_match,long_literals,bench20481", "1"], capture_output=True, text=True)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert "3 blocks, 0 differ from the oracle" in r.stdout, r.stdout
+
+
+@pytest.mark.parametrize("level", [2, -5])
+def test_emulated_workgroup_takes_many_blocks(emu, level):
+    """One emulated workgroup over zstd_big_inputs.reuse_sequence(): every
+    block after the first is compressed in the slot and the LDS its
+    predecessor left (longer, shorter, raw-exit, all-zero; blocks of the first
+    kernel skipped in between), under AddressSanitizer and UBSan, at the
+    levels the edge-block test does not run. The emulator's barriers are real
+    ones: this holds the carry-over, not the device's ordering
+    (tests/test_codec_reuse_and_bounds.py)."""
+    nb = len(zb.reuse_sequence())
+    r = subprocess.run([sys.executable, str(REPO / "tools/simt_emu/zstdc_check.py"), "reuse",
+                        str(level)], capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert f"{nb} blocks, 0 differ from the oracle" in r.stdout, r.stdout
+    assert "Sanitizer" not in r.stdout + r.stderr and "runtime error" not in r.stdout + r.stderr, \
+        (r.stdout + r.stderr)[-3000:]
 
 
 # ---- GPU -----------------------------------------------------------------------
@@ -151,7 +168,7 @@ def test_edge_blocks(lvkv, gpu, level):
     torch.cuda.synchronize()
     assert st.cpu().tolist() == [lvkv.ZSTD_OK] * len(blobs)
     got = _unpack(dst, doff, dlen)
-    bad = [n for n, x, g in zip(names, blobs, got) if g != _frame(x, level)]
+    bad = [n for n, x, g in zip(names, blobs, got) if g != zb.frame(x, level)]
     assert not bad, f"level {level}: device frame differs from the oracle on {bad}"
     # the blocks of the first kernel: the bytes zstd_compress gives
     small = [k for k, x in enumerate(blobs) if len(x) <= lvkv.ZSTD_COMPRESS_MAX_BLOCK]
@@ -172,7 +189,7 @@ def test_edge_statuses(lvkv, gpu):
         dst, doff, dlen, st = lvkv.zstd_compress_big(src, off, ln, level=level, max_len=1 << 30)
         torch.cuda.synchronize()
         assert st.cpu().tolist() == [lvkv.ZSTD_TOO_LARGE] + [lvkv.ZSTD_OK] * 3
-        assert _unpack(dst, doff, dlen)[1:] == [_frame(x, level) for x in blobs[1:]]
+        assert _unpack(dst, doff, dlen)[1:] == [zb.frame(x, level) for x in blobs[1:]]
     # max_len below the kernel's own bound
     _, _, _, st = lvkv.zstd_compress_big(src, off, ln, level=1, max_len=30000)
     torch.cuda.synchronize()
@@ -205,7 +222,7 @@ def test_no_dependence_on_neighbouring_bytes(lvkv, gpu):
         torch.cuda.synchronize()
         assert st.cpu().tolist() == [lvkv.ZSTD_OK] * 3
         got = _unpack(dst, doff, dlen)
-        assert got[0] == got[1] == got[2] == _frame(x, level)
+        assert got[0] == got[1] == got[2] == zb.frame(x, level)
 
 
 @functools.lru_cache(maxsize=1)
@@ -311,7 +328,7 @@ def test_reported_raw_block(lvkv, gpu):
     img = file.cpu().numpy()
     for k in (0, 2):
         o, n = int(hoff[k].item()), int(hsize[k].item())
-        assert img[o:o + n].tobytes() == _frame(raws[k], 1)
+        assert img[o:o + n].tobytes() == zb.frame(raws[k], 1)
     _read_back(lvkv, torch, gpu, file, hoff, hsize, raws)
 
 

@@ -1,5 +1,6 @@
-"""The inputs of the any-size write path's tests (tests/test_write_any_size.py),
-rebuilt from seeds: the generator of the library pins
+"""The inputs of the any-size write path's tests (tests/test_write_any_size.py,
+tests/test_codec_reuse_and_bounds.py) and the oracle's frames of them, cached
+for all of those; rebuilt from seeds: the generator of the library pins
 (tests/golden/gen_zstd_write_big.py), the tests and the CPU emulator's check
 (tools/simt_emu/zstdc_check.py) all take them from here, so that a pinned
 hash, a device frame and an emulated frame speak of the same bytes.
@@ -43,6 +44,46 @@ def edge_blocks():
 
 def edge(name: str) -> bytes:
     return dict(edge_blocks())[name]
+
+
+@functools.lru_cache(maxsize=None)
+def frame(x: bytes, level: int) -> bytes:
+    """The oracle's frame, computed once per (block, level) for all tests."""
+    import zstd_encoder as ze
+    return ze.compress(x, level)
+
+
+@functools.lru_cache(maxsize=1)
+def reuse_pool():
+    """[(name, bytes)]: the distinct big blocks of the reuse tests
+    (tests/test_codec_reuse_and_bounds.py): the 16 big edge blocks, whose
+    frames test_edge_blocks computes anyway, and 24 blocks of 20,481-40,000
+    bytes, cheap for the oracle."""
+    out = [(n, x) for n, x in edge_blocks() if len(x) > 20480]
+    out += [(f"fuzz{k}_{len(x)}", x)
+            for k, x in enumerate(fuzz_inputs(np.random.default_rng(11), 24, 20481, 40000))]
+    return out
+
+
+@functools.lru_cache(maxsize=1)
+def reuse_sequence():
+    """[(name, bytes)]: what one emulated workgroup pulls in a row
+    (tools/simt_emu/zstdc_check.py reuse): long then short, compressible, the
+    raw exit (random) and all-zero in turn, blocks of the first kernel in
+    between. Under 200 KiB in all: the emulator takes 0.15 s a KiB."""
+    b = bench()
+    rng = np.random.default_rng(13)
+
+    def rand(n):
+        return rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+
+    skewed = np.minimum(rng.geometric(0.6, 34000) - 1, 255).astype(np.uint8).tobytes()
+    out = [("bench40000", b[:40000]), ("abc", b"abc"), ("random20481", rand(20481)),
+           ("zeros32769", bytes(32769)), ("empty", b""), ("skewed34000", skewed),
+           ("bench4096", b[:4096]), ("random21000", rand(21000)),
+           ("periodic30000", (b"abcdefg" * 5000)[:30000]), ("bench20481", b[:20481])]
+    assert sum(len(x) for _, x in out) <= 200 * 1024
+    return out
 
 
 def fuzz_inputs(rng, count, lo, hi):

@@ -3,10 +3,15 @@ blocks and compare every frame with the oracle's (CPU debugging aid).
 
     python tools/simt_emu/zstdc_check.py [fixtures|bench N|fuzz N SEED] [level]
     python tools/simt_emu/zstdc_check.py big NAME[,NAME...] LEVEL
+    python tools/simt_emu/zstdc_check.py reuse LEVEL
 
 `big` runs edge blocks of tests/zstd_big_inputs.py (by name, or `all`)
 through the call for blocks up to 128 KiB: the first kernel, then the
 persistent one out of a scratch of exactly the size the C-ABI asks for.
+`reuse` runs zstd_big_inputs.reuse_sequence() through the same call: the one
+emulated workgroup pulls every block, so each but the first is compressed in
+a slot and an LDS the block before it left behind. (The emulator's barriers
+are real ones: it checks the carry-over, not the device's ordering.)
 """
 from __future__ import annotations
 
@@ -38,6 +43,9 @@ def blocks(kind, args):
         import zstd_big_inputs as zb
         names = [n for n, _ in zb.edge_blocks()] if args[0] == "all" else args[0].split(",")
         return [zb.edge(n) for n in names]
+    if kind == "reuse":
+        import zstd_big_inputs as zb
+        return [x for _, x in zb.reuse_sequence()]
     if kind == "bench":
         from tools.db_bench_data import block_batch
         n = int(args[0])
@@ -52,7 +60,7 @@ def main():
     kind = sys.argv[1] if len(sys.argv) > 1 else "bench"
     rest = sys.argv[2:]
     level = 1
-    if rest and rest[-1].lstrip("-").isdigit() and kind in ("fixtures", "big"):
+    if rest and rest[-1].lstrip("-").isdigit() and kind in ("fixtures", "big", "reuse"):
         level = int(rest[-1])
     ins = blocks(kind, rest)
     exe = REPO / "build" / "simt_emu" / "zstdc_emu"
@@ -60,7 +68,7 @@ def main():
         d = Path(d)
         (d / "in.bin").write_bytes(b"".join(ins))
         (d / "lens.u32").write_bytes(np.array([len(x) for x in ins], dtype=np.uint32).tobytes())
-        mx = 131072 if kind == "big" else max(16, max(len(x) for x in ins))
+        mx = 131072 if kind in ("big", "reuse") else max(16, max(len(x) for x in ins))
         r = subprocess.run([str(exe), str(d / "in.bin"), str(d / "lens.u32"), str(level), str(mx),
                             str(d / "out.bin"), str(d / "ol.u32")], capture_output=True, text=True)
         if r.returncode:
