@@ -178,6 +178,84 @@ int lvkv_sst_write_blocks_status_device(const void* d_raw, const uint64_t* d_raw
                                         uint8_t* d_type, uint64_t* d_end, size_t scratch_bytes,
                                         uint8_t* d_status, void* stream);
 
+/* ---- the whole table: TableBuilder::Finish on the device ------------------- */
+
+#define LVKV_TABLE_OK 0
+#define LVKV_TABLE_BAD_BLOCK 1    /* a data block is not a block BlockBuilder::Finish returns:
+                                     restart count or offset outside the block, a restart that
+                                     is not where an entry starts, a varint or entry past its
+                                     run's end, shared longer than the previous key or not 0 at
+                                     a restart, no entries, an internal key under 8 bytes */
+#define LVKV_TABLE_KEY_TOO_LONG 2 /* a key longer than max_key_len */
+#define LVKV_TABLE_CAPACITY 3     /* the image does not fit in file_capacity */
+
+typedef struct lvkv_sst_table_report {
+  int32_t status;           /* LVKV_TABLE_* */
+  uint32_t first_bad_block; /* for BAD_BLOCK / KEY_TOO_LONG (whose verdict status is), else
+                               0xFFFFFFFF */
+  uint64_t num_entries;     /* TableBuilder::NumEntries */
+  uint32_t nfilters;        /* entries of the filter block's offset array */
+  uint8_t meta_type, index_type;     /* block types as written (0/1/2) */
+  uint8_t meta_status, index_status; /* codec verdicts, as d_status[] */
+  uint64_t data_end;                 /* the first byte after the data blocks */
+  uint64_t filter_offset, filter_size; /* 0, 0 without a filter policy */
+  uint64_t meta_offset, meta_size, index_offset, index_size;
+  uint64_t file_size;                /* TableBuilder::FileSize; 0 unless status is OK */
+} lvkv_sst_table_report;
+
+/*
+ * Scratch for lvkv_sst_write_table_device: enough for any nblocks blocks of
+ * total_raw_bytes in all, whatever the compression (it holds the ragged
+ * scratch of lvkv_sst_write_blocks_status_device for the data blocks and for
+ * the metaindex and index blocks, one key of max_key_len a block and a lane,
+ * and the per-block arrays). The call itself knows no total: it needs at
+ * least the value for total_raw_bytes 0, and a data block whose compressed
+ * form finds no room is written raw and reported LVKV_ZSTD_TOO_LARGE.
+ */
+size_t lvkv_sst_write_table_scratch_bytes(size_t nblocks, uint64_t total_raw_bytes,
+                                          uint32_t max_len, uint32_t max_key_len,
+                                          int filter_bits_per_key);
+/* An upper bound of the file: every block raw, every entry 3 bytes. */
+uint64_t lvkv_sst_table_file_bound(size_t nblocks, uint64_t total_raw_bytes, uint32_t max_key_len,
+                                   int filter_bits_per_key);
+
+/*
+ * TableBuilder::Flush per block and TableBuilder::Finish (table/
+ * table_builder.cc:104-268) in one stream-ordered call: the data blocks
+ * d_raw[d_raw_off[i], + d_raw_len[i]) in key order, each the bytes
+ * BlockBuilder::Finish returns, become the whole table image in d_file from
+ * offset 0 -- the data blocks as lvkv_sst_write_blocks_status_device writes
+ * them (compression, zstd_level, max_len, d_handle_*, d_type, d_status as
+ * there), the filter block (table/filter_block.cc; filter_bits_per_key > 0:
+ * NewBloomFilterPolicy(bits), 0: no policy, no filter block), the metaindex
+ * block, the index block (restart interval 1, separators by
+ * FindShortestSeparator / FindShortSuccessor) and the footer. key_format 0:
+ * keys are byte strings under BytewiseComparator and the filter hashes whole
+ * keys; 1: internal keys under InternalKeyComparator, the filter hashes user
+ * keys (InternalFilterPolicy), as db/builder.cc builds tables. The metaindex
+ * and index blocks go through the same writer: d_report->meta_status /
+ * index_status are its verdicts (an index block past 128 KiB stays raw under
+ * zstd and is LVKV_ZSTD_TOO_LARGE; the table is valid and its status OK).
+ *
+ * No synchronisation, no copy to the host: d_report (device memory) says how
+ * it went. On a status other than OK nothing is written at or past d_file +
+ * file_capacity, file_size is 0 and the bytes from data_end on are
+ * unspecified; the data blocks that fit and the four arrays are as the block
+ * writer leaves them. LVKV_ERR_INVALID, before any launch: a null pointer
+ * (d_raw, d_raw_off, d_raw_len and the four arrays may be null when nblocks
+ * is 0), compression outside 0..2, key_format outside 0..1, zstd level 0 or
+ * >= 3 with compression 2, filter_bits_per_key < 0, max_key_len > 2^20,
+ * nblocks x (max_key_len + 26) >= 2^32, scratch_bytes under the sizing
+ * function's value for total_raw_bytes 0.
+ */
+int lvkv_sst_write_table_device(const void* d_raw, const uint64_t* d_raw_off,
+                                const uint32_t* d_raw_len, size_t nblocks, int compression,
+                                int zstd_level, uint32_t max_len, int key_format,
+                                int filter_bits_per_key, uint32_t max_key_len, void* d_scratch,
+                                size_t scratch_bytes, void* d_file, uint64_t file_capacity,
+                                uint64_t* d_handle_off, uint32_t* d_handle_size, uint8_t* d_type,
+                                uint8_t* d_status, lvkv_sst_table_report* d_report, void* stream);
+
 /* ReadBlock verdicts */
 #define LVKV_READ_OK 0
 #define LVKV_READ_CHECKSUM 1        /* "block checksum mismatch" (table/format.cc:95-98) */

@@ -173,6 +173,13 @@ def _load() -> ctypes.CDLL:
     L.lvkv_sst_write_blocks_status_device.argtypes = [vp, vp, vp, sz, i32, i32, u32, vp, vp, u64,
                                                       vp, vp, vp, vp, sz, vp, vp]
     L.lvkv_sst_write_blocks_status_device.restype = i32
+    L.lvkv_sst_write_table_scratch_bytes.argtypes = [sz, u64, u32, u32, i32]
+    L.lvkv_sst_write_table_scratch_bytes.restype = sz
+    L.lvkv_sst_table_file_bound.argtypes = [sz, u64, u32, i32]
+    L.lvkv_sst_table_file_bound.restype = u64
+    L.lvkv_sst_write_table_device.argtypes = [vp, vp, vp, sz, i32, i32, u32, i32, i32, u32, vp, sz,
+                                              vp, u64, vp, vp, vp, vp, vp, vp]
+    L.lvkv_sst_write_table_device.restype = i32
     L.lvkv_sst_read_blocks_device.argtypes = [vp, vp, vp, sz, i32, vp, vp, vp, vp, vp, u32, vp]
     L.lvkv_sst_read_blocks_device.restype = i32
     L.lvkv_strerror.argtypes = [i32]
@@ -863,6 +870,85 @@ def sst_write_blocks_status(raw, offsets, lengths, *, compression: int = 1, zstd
     int64 tensor of one, status uint8)."""
     return _sst_write(raw, offsets, lengths, compression, zstd_level, max_len, file, file_offset,
                       stream, True)
+
+
+TABLE_OK, TABLE_BAD_BLOCK, TABLE_KEY_TOO_LONG, TABLE_CAPACITY = range(4)
+
+
+class SstTableReport(ctypes.Structure):
+    """lvkv_sst_table_report (include/lvkv_snappy.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("first_bad_block", ctypes.c_uint32),
+                ("num_entries", ctypes.c_uint64), ("nfilters", ctypes.c_uint32),
+                ("meta_type", ctypes.c_uint8), ("index_type", ctypes.c_uint8),
+                ("meta_status", ctypes.c_uint8), ("index_status", ctypes.c_uint8),
+                ("data_end", ctypes.c_uint64), ("filter_offset", ctypes.c_uint64),
+                ("filter_size", ctypes.c_uint64), ("meta_offset", ctypes.c_uint64),
+                ("meta_size", ctypes.c_uint64), ("index_offset", ctypes.c_uint64),
+                ("index_size", ctypes.c_uint64), ("file_size", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def sst_write_table(raw, offsets, lengths, *, compression: int = 1, zstd_level: int = 1,
+                    max_len: Optional[int] = None, key_format: int = 1,
+                    filter_bits_per_key: int = 10, max_key_len: int = 256, file=None,
+                    file_capacity: Optional[int] = None, scratch=None, stream=None):
+    """TableBuilder::Flush per block and TableBuilder::Finish (table/
+    table_builder.cc) in one stream-ordered call (lvkv_sst_write_table_device):
+    the finished data blocks raw[offsets[i] : offsets[i] + lengths[i]], in key
+    order, become the whole table image -- data blocks as
+    sst_write_blocks_status writes them, filter block (filter_bits_per_key > 0:
+    the built-in Bloom policy; 0: none), metaindex block, index block, footer.
+    key_format 1: internal keys (db/builder.cc's tables), 0: plain byte
+    strings. `file` (allocated by lvkv_sst_table_file_bound when None) holds
+    the image from offset 0; at most file_capacity (default: all) of its bytes
+    are written. Returns (file, handle offsets int64, handle sizes int32,
+    types uint8, status uint8, report dict); report['status'] is TABLE_*, and
+    the image is file[:report['file_size']] when it is TABLE_OK. The report is
+    the one thing read back."""
+    torch = _torch()
+    n = offsets.numel()
+    dev = raw.device
+    if lengths.numel() != n:
+        raise ValueError("offsets and lengths differ in length")
+    total_raw = int(lengths.to(torch.int64).sum().item()) if n else 0
+    if max_len is None:
+        max_len = int(lengths.max().item()) if n else 0
+    max_len = max(0, min(int(max_len), 0xFFFFFFFF))
+    if file is None:
+        file = torch.zeros(int(_lib.lvkv_sst_table_file_bound(n, total_raw, max_key_len,
+                                                              filter_bits_per_key)),
+                           dtype=torch.uint8, device=dev)
+    if file_capacity is None:
+        file_capacity = file.numel()
+    if file_capacity > file.numel():
+        raise ValueError("file_capacity exceeds the file tensor")
+    if scratch is None:
+        scratch = torch.empty(int(_lib.lvkv_sst_write_table_scratch_bytes(
+            n, total_raw, max_len, max_key_len, filter_bits_per_key)), dtype=torch.uint8,
+            device=dev)
+    hoff = torch.empty(n, dtype=torch.int64, device=dev)
+    hsize = torch.empty(n, dtype=torch.int32, device=dev)
+    typ = torch.empty(n, dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    rep = torch.zeros(ctypes.sizeof(SstTableReport), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lvkv_sst_write_table_device(
+            _dev_ptr(raw, "raw", (torch.uint8, torch.int8)) if n else None,
+            _dev_ptr(offsets, "offsets", (torch.int64,)) if n else None,
+            _dev_ptr(lengths, "lengths", (torch.int32,)) if n else None, n, int(compression),
+            int(zstd_level), max_len, int(key_format), int(filter_bits_per_key), int(max_key_len),
+            _dev_ptr(scratch, "scratch", (torch.uint8, torch.int8)), scratch.numel(),
+            _dev_ptr(file, "file", (torch.uint8, torch.int8)), int(file_capacity),
+            _dev_ptr(hoff, "hoff") if n else None, _dev_ptr(hsize, "hsize") if n else None,
+            _dev_ptr(typ, "type") if n else None, _dev_ptr(status, "status") if n else None,
+            _dev_ptr(rep, "report"), _stream_handle(stream, dev))
+    _check("lvkv_sst_write_table_device", rc)
+    if stream is not None:
+        stream.synchronize()
+    report = SstTableReport.from_buffer_copy(bytes(rep.cpu().numpy())).as_dict()
+    return file, hoff, hsize, typ, status, report
 
 
 def sst_read_blocks(file, handle_off, handle_size, *, max_ulen: int, verify: bool = True,

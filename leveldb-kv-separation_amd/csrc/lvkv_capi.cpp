@@ -925,6 +925,134 @@ int lvkv_sst_write_blocks_status_device(const void* d_raw, const uint64_t* d_raw
                                        stream);
 }
 
+size_t lvkv_sst_write_table_scratch_bytes(size_t nblocks, uint64_t total_raw_bytes,
+                                          uint32_t max_len, uint32_t max_key_len,
+                                          int filter_bits_per_key) {
+  // alignment slack, the finisher's own part, the data blocks' ragged scratch
+  return 256u + sst_finish_plan(nblocks, max_key_len, filter_bits_per_key).fixed +
+         sst_write_v2_envelope(nblocks, total_raw_bytes, max_len);
+}
+
+uint64_t lvkv_sst_table_file_bound(size_t nblocks, uint64_t total_raw_bytes, uint32_t max_key_len,
+                                   int filter_bits_per_key) {
+  const uint64_t n = nblocks;
+  const uint64_t data = total_raw_bytes + 5 * n;
+  uint64_t filter = 0;
+  if (filter_bits_per_key > 0) {
+    // an entry takes 3 bytes or more; a filter of k keys max(64, k * bits)
+    // bits rounded up and a probe count, at most one with keys a block; an
+    // offset per 2 KiB of data and one; the array's offset, the base, the trailer
+    const uint64_t keys = total_raw_bytes / 3;
+    filter = keys * static_cast<uint64_t>(filter_bits_per_key) / 8 + 10 * n +
+             4 * (data / 2048 + 1) + 5 + 5;
+  }
+  const uint64_t index = sst_finish_plan(nblocks, max_key_len, filter_bits_per_key).index_cap;
+  return data + filter + (kSstMetaRoom + 5) + (index + 5) + 48;
+}
+
+// lvkv_sst_fill_trailers_device over the first min(n, *d_count) handles.
+static int fill_trailers_counted(void* d_file, const uint64_t* d_offsets, const uint32_t* d_sizes,
+                          size_t n, const uint32_t* d_count, hipStream_t stream) {
+  KernelArgs a = blank_args();
+  a.base = static_cast<const uint8_t*>(d_file);
+  a.offsets = d_offsets;
+  a.lengths = d_sizes;
+  a.mode = kModeSstFill;
+  a.count = d_count;
+  return run_batch(a, n, stream);
+}
+
+int lvkv_sst_write_table_device(const void* d_raw, const uint64_t* d_raw_off,
+                                const uint32_t* d_raw_len, size_t nblocks, int compression,
+                                int zstd_level, uint32_t max_len, int key_format,
+                                int filter_bits_per_key, uint32_t max_key_len, void* d_scratch,
+                                size_t scratch_bytes, void* d_file, uint64_t file_capacity,
+                                uint64_t* d_handle_off, uint32_t* d_handle_size, uint8_t* d_type,
+                                uint8_t* d_status, lvkv_sst_table_report* d_report, void* stream) {
+  if (!d_scratch || !d_file || !d_report) return LVKV_ERR_INVALID;
+  if (nblocks != 0 && (!d_raw || !d_raw_off || !d_raw_len || !d_handle_off || !d_handle_size ||
+                       !d_type || !d_status))
+    return LVKV_ERR_INVALID;
+  if (compression < 0 || compression > 2 || key_format < 0 || key_format > 1 ||
+      filter_bits_per_key < 0 || max_key_len > (1u << 20))
+    return LVKV_ERR_INVALID;
+  if (compression == 2 && (zstd_level == 0 || zstd_level > 2)) return LVKV_ERR_INVALID;
+  // (u32 block indices in every kernel; the index block's length is a u32)
+  if (nblocks > kMaxBlocksPerLaunch ||
+      uint64_t{nblocks} * (uint64_t{max_key_len} + 26) + 8 > 0xffffffffull)
+    return LVKV_ERR_INVALID;
+  if (scratch_bytes < lvkv_sst_write_table_scratch_bytes(nblocks, 0, max_len, max_key_len,
+                                                         filter_bits_per_key))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  const uint32_t n = static_cast<uint32_t>(nblocks);
+
+  SstFinishArgs f{};
+  f.raw = static_cast<const uint8_t*>(d_raw);
+  f.raw_off = d_raw_off;
+  f.raw_len = d_raw_len;
+  f.nblocks = n;
+  f.key_format = static_cast<uint32_t>(key_format);
+  f.bits_per_key = static_cast<uint32_t>(filter_bits_per_key);
+  // BloomFilterPolicy's constructor (util/bloom.cc:19-24)
+  size_t k = static_cast<size_t>(filter_bits_per_key * 0.69);
+  if (k < 1) k = 1;
+  if (k > 30) k = 30;
+  f.k = static_cast<uint32_t>(k);
+  f.max_key_len = max_key_len;
+  uint8_t* const scratch = static_cast<uint8_t*>(d_scratch);
+  f.base = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(scratch) + 255u) &
+                                      ~uintptr_t{255});
+  f.plan = sst_finish_plan(nblocks, max_key_len, filter_bits_per_key);
+  f.file = static_cast<uint8_t*>(d_file);
+  f.cap = file_capacity;
+  f.hoff = d_handle_off;
+  f.hsize = d_handle_size;
+  f.report = d_report;
+  SstFinishCtl* ctl = reinterpret_cast<SstFinishCtl*>(f.base);
+
+  hipError_t e = launch_sst_finish(f, 0, hs);
+  if (e != hipSuccess) return hip_fail(e);
+  // the data blocks, from file offset 0
+  uint8_t* const data_scratch = f.base + f.plan.fixed;
+  const SstWriteScratch ds =
+      compression == 0 || n == 0
+          ? SstWriteScratch{}
+          : sst_scratch_ragged(data_scratch,
+                               scratch_bytes - static_cast<size_t>(data_scratch - scratch), n,
+                               compression == 2 ? max_len : 0u);
+  const SstWriteDest data_dest{nullptr, file_capacity, &ctl->nfit_data};
+  e = launch_sst_write_blocks(f.raw, d_raw_off, d_raw_len, n, compression, max_len, ds, f.file, 0,
+                              d_handle_off, d_handle_size, d_type, &ctl->data_end, zstd_level,
+                              d_status, hs, &data_dest);
+  if (e != hipSuccess) return hip_fail(e);
+  rc = fill_trailers_counted(d_file, d_handle_off, d_handle_size, n, &ctl->nfit_data, hs);
+  if (rc != LVKV_OK) return rc;
+  // the filter block in place, the metaindex and index contents in the scratch
+  e = launch_sst_finish(f, 1, hs);
+  if (e != hipSuccess) return hip_fail(e);
+  // [metaindex, index] through the same writer, from the offset stage 1 left
+  const SstWriteScratch ts =
+      compression == 0
+          ? SstWriteScratch{}
+          : sst_scratch_ragged(f.base + f.plan.tail_scratch, f.plan.tail_scratch_bytes, 2,
+                               compression == 2 ? f.plan.tail_max_len : 0u);
+  const SstWriteDest tail_dest{&ctl->tail_base, file_capacity, &ctl->nfit_tail};
+  e = launch_sst_write_blocks(f.base + f.plan.tail_raw, ctl->t_raw_off, ctl->t_raw_len, 2,
+                              compression, f.plan.tail_max_len, ts, f.file, 0, ctl->t_hoff + 1,
+                              ctl->t_hsize + 1, ctl->t_type, &ctl->tail_end, zstd_level,
+                              ctl->t_status, hs, &tail_dest);
+  if (e != hipSuccess) return hip_fail(e);
+  e = launch_sst_finish(f, 2, hs);
+  if (e != hipSuccess) return hip_fail(e);
+  // the trailers of the filter block (where there is one) and of the two
+  const size_t first = filter_bits_per_key != 0 ? 0 : 1;
+  return fill_trailers_counted(d_file, ctl->t_hoff + first, ctl->t_hsize + first, 3 - first,
+                               &ctl->tail_count, hs);
+}
+
 int lvkv_sst_write_blocks_device(const void* d_raw, const uint64_t* d_raw_off,
                                  const uint32_t* d_raw_len, size_t nblocks, int compression,
                                  uint32_t max_len, void* d_scratch, void* d_file,

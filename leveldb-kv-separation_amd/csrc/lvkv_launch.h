@@ -13,6 +13,7 @@
 
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
+#include "lvkv_snappy.h"
 
 namespace lvkv {
 
@@ -150,17 +151,90 @@ uint64_t sst_write_v2_fixed(size_t nblocks, uint32_t max_len);
 uint64_t sst_write_v2_bytes(size_t nblocks, uint64_t total_raw, uint32_t max_len);
 SstWriteScratch sst_scratch_ragged(uint8_t* scratch, uint64_t scratch_bytes, uint32_t nblocks,
                                    uint32_t pool_max_len);
-// status: the codec's verdict per block, or nullptr.
+// For a call whose place in the file an earlier kernel of the stream decides
+// (the table writer's metaindex and index blocks): the first block's file
+// offset is read from *base on the device instead of file_offset (nullptr:
+// file_offset), nothing is written at or past file + cap, and *nfit (when not
+// null) = how many blocks, a prefix, ended at or before cap.
+struct SstWriteDest {
+  const uint64_t* base;
+  uint64_t cap;
+  uint32_t* nfit;
+};
+// status: the codec's verdict per block, or nullptr. dest: nullptr for the
+// host's file_offset and a file that holds everything.
 hipError_t launch_sst_write_blocks(const uint8_t* raw, const uint64_t* raw_off,
                                    const uint32_t* raw_len, uint32_t nblocks, int compression,
                                    uint32_t max_len, const SstWriteScratch& s, uint8_t* file,
                                    uint64_t file_offset, uint64_t* hoff, uint32_t* hsize,
                                    uint8_t* type, uint64_t* end, int zstd_level, uint8_t* status,
-                                   hipStream_t stream);
+                                   hipStream_t stream, const SstWriteDest* dest = nullptr);
 hipError_t launch_sst_read_blocks(const uint8_t* file, const uint64_t* hoff, const uint32_t* hsize,
                                   uint32_t nblocks, uint8_t* out, const uint64_t* out_off,
                                   const uint32_t* out_cap, uint32_t* out_len, uint8_t* status,
                                   const uint8_t* vstatus, uint32_t max_ulen, hipStream_t stream);
+
+// ---- TableBuilder::Finish on the device (lvkv_sst_finish.hip) ---------------
+
+// The words the kernels of one lvkv_sst_write_table_device call hand to each
+// other and to the two writer calls around them, at the head of the scratch.
+struct SstFinishCtl {
+  uint64_t data_end;       // the data blocks' writer: the offset after them
+  uint64_t tail_base;      // where the metaindex block goes (kNowhere: nothing is built)
+  uint64_t tail_end;       // the tail's writer: the offset after the index block
+  uint64_t nkeys;
+  uint64_t filter_bytes;   // the filters alone, without the offset array
+  uint64_t filter_size;    // the filter block's contents
+  uint64_t index_entries;  // the index block's entries, without its restarts
+  uint64_t t_hoff[3];      // handles of the filter, metaindex and index blocks
+  uint64_t t_raw_off[2];   // metaindex and index contents in the tail image
+  uint32_t t_hsize[3];
+  uint32_t t_raw_len[2];
+  uint32_t nfit_data, nfit_tail;  // SstWriteDest::nfit of the two writer calls
+  uint32_t tail_count;     // the tail handles whose trailers get a CRC
+  uint32_t first_bad;      // lowest block the key scan rejected, 0xFFFFFFFF: none
+  uint32_t ok;             // 1: every data block is sound and in the file
+  uint32_t nfilters;
+  uint8_t t_type[2], t_status[2];
+};
+// Byte offsets of the call's arrays from the 256-aligned start of its scratch.
+// Everything before `fixed` depends on the host's arguments alone; the data
+// blocks' ragged writer scratch takes what follows.
+struct SstFinishPlan {
+  uint64_t kx, fo, fsz, io;  // u64 a block (kx: one more)
+  uint64_t cnt, first_off, first_len, last_len, head, next_head, sep_d, klen, esz;  // u32
+  uint64_t verdict;          // u8
+  uint64_t last_key;         // max_key_len a block
+  uint64_t key_buf;          // max_key_len a lane of the bit-setting grid (keys past LDS)
+  uint64_t tail_raw;         // the metaindex contents (kMetaRoom), then the index's
+  uint64_t tail_scratch, tail_scratch_bytes;  // the tail's ragged writer scratch
+  uint64_t index_cap;        // the longest index block of nblocks entries
+  uint64_t fixed;
+  uint32_t tail_max_len;     // the tail writer's max_len: min(index_cap, 128 KiB)
+  uint32_t bits_groups;      // workgroups of the bit-setting grid
+};
+constexpr uint32_t kSstMetaRoom = 128;
+// sst_write_v2_bytes, never smaller for a larger max_len.
+uint64_t sst_write_v2_envelope(size_t nblocks, uint64_t total_raw, uint32_t max_len);
+SstFinishPlan sst_finish_plan(size_t nblocks, uint32_t max_key_len, int filter_bits_per_key);
+struct SstFinishArgs {
+  const uint8_t* raw;
+  const uint64_t* raw_off;
+  const uint32_t* raw_len;
+  uint32_t nblocks;
+  uint32_t key_format, bits_per_key, k, max_key_len;
+  uint8_t* base;  // the aligned scratch: SstFinishCtl, then the plan's arrays
+  SstFinishPlan plan;
+  uint8_t* file;
+  uint64_t cap;
+  const uint64_t* hoff;  // the data blocks' handles
+  const uint32_t* hsize;
+  lvkv_sst_table_report* report;
+};
+// stage 0: the control words, before the data blocks' writer; 1: everything
+// between that writer and the tail's (key scan, filter block in place at
+// data_end, metaindex and index contents); 2: footer and report, after it.
+hipError_t launch_sst_finish(const SstFinishArgs& a, int stage, hipStream_t stream);
 
 #ifdef LVKV_PROBE_BUILD
 // Probe builds (tools/probe/liblvkv_probe.so): timestamp buffers and knobs

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lvkv_block_scan.h"
 #include "lvkv_launch.h"
 #include "lvkv_snappy.h"
 
@@ -646,40 +647,6 @@ __global__ void __launch_bounds__(64) snappy_uncompress_big_kernel(UncompressArg
 
 // ---- TableBuilder::WriteBlock over a batch (table/table_builder.cc:141-209) --
 
-__device__ __forceinline__ uint64_t shfl_up64(uint64_t v, uint32_t d) {
-  const uint32_t lo = __shfl_up(static_cast<uint32_t>(v), d);
-  const uint32_t hi = __shfl_up(static_cast<uint32_t>(v >> 32), d);
-  return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
-// Exclusive scan of `local` over the workgroup's 1,024 threads: the sum of the
-// threads before this one, and in *total the sum of all. wsum: 17 u64 of LDS;
-// a barrier stands between a return and the next call (the caller's, after
-// its stores).
-__device__ __forceinline__ uint64_t block_scan(uint64_t local, uint64_t* wsum, uint64_t* total) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  uint64_t incl = local;
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint64_t y = shfl_up64(incl, d);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) wsum[w] = incl;
-  __syncthreads();
-  if (w == 0) {
-    const uint64_t v = lane < 16 ? wsum[lane] : 0;
-    uint64_t s = v;
-    for (uint32_t d = 1; d < 16; d <<= 1) {
-      const uint64_t y = shfl_up64(s, d);
-      if (lane >= d) s += y;
-    }
-    if (lane < 16) wsum[lane] = s - v;  // exclusive
-    if (lane == 15) wsum[16] = s;       // the pass's total
-  }
-  __syncthreads();
-  *total = wsum[16];
-  return wsum[w] + incl - local;
-}
-
 // A block's slot for its compressed form: room for either codec's bound,
 // rounded to 16.
 __host__ __device__ constexpr uint64_t sst_slot_bytes(uint32_t n) {
@@ -731,22 +698,29 @@ __global__ void __launch_bounds__(256) sst_status_kernel(uint8_t* cst, const uin
 // Which form each block keeps and where it lands: the compressed form when
 // it is smaller than raw - raw/8 (table_builder.cc:160-168), else raw with
 // type kNoCompression; handles are an exclusive scan of size + 5 (the
-// trailer, :206) from file_offset. One workgroup, 4 blocks a thread a pass.
+// trailer, :206) from file_offset, or from *base where an earlier kernel of
+// the stream left the offset on the device. nfit (where asked for) = the
+// blocks, a prefix, that end at or before `cap`. One workgroup, 4 blocks a
+// thread a pass.
 __global__ void __launch_bounds__(1024) sst_layout_kernel(const uint32_t* raw_len,
                                                           const uint32_t* clen, const uint8_t* cst,
                                                           uint32_t n, uint64_t file_offset,
                                                           uint64_t* hoff, uint32_t* hsize,
                                                           uint8_t* type, uint64_t* end,
-                                                          uint32_t ctype) {
+                                                          uint32_t ctype, const uint64_t* base,
+                                                          uint64_t cap, uint32_t* nfit) {
   __shared__ uint64_t wsum[17];
+  __shared__ uint32_t fit;
   const uint32_t t = threadIdx.x;
-  uint64_t carry = file_offset;
-  for (uint32_t base = 0; base < n; base += 4096) {
+  if (t == 0) fit = 0;
+  uint64_t carry = base != nullptr ? *base : file_offset;
+  uint32_t mine = 0;
+  for (uint32_t base_i = 0; base_i < n; base_i += 4096) {
     uint32_t sz[4];
     uint8_t ty[4];
     uint64_t local = 0;
     for (uint32_t j = 0; j < 4; ++j) {
-      const uint32_t i = base + 4 * t + j;
+      const uint32_t i = base_i + 4 * t + j;
       sz[j] = 0;
       ty[j] = 0;
       if (i < n) {
@@ -760,34 +734,42 @@ __global__ void __launch_bounds__(1024) sst_layout_kernel(const uint32_t* raw_le
     uint64_t total;
     uint64_t at = carry + block_scan(local, wsum, &total);
     for (uint32_t j = 0; j < 4; ++j) {
-      const uint32_t i = base + 4 * t + j;
+      const uint32_t i = base_i + 4 * t + j;
       if (i < n) {
         hoff[i] = at;
         hsize[i] = sz[j];
         type[i] = ty[j];
         at += sz[j] + 5u;
+        if (at <= cap) ++mine;
       }
     }
     carry += total;
     __syncthreads();
   }
+  if (nfit != nullptr) {
+    if (mine) atomicAdd(&fit, mine);
+    __syncthreads();
+    if (t == 0) *nfit = fit;
+  }
   if (t == 0) *end = carry;
 }
 
 // WriteRawBlock's bytes but the CRC (table_builder.cc:195-204): the kept
-// contents at the handle, the type byte after them. The masked CRC is the
-// batch CRC kernel's (lvkv_sst_fill_trailers_device) over the same handles.
+// contents at the handle, the type byte after them; a block whose trailer
+// would end past `cap` is left out. The masked CRC is the batch CRC kernel's
+// (lvkv_sst_fill_trailers_device) over the same handles.
 __global__ void __launch_bounds__(256) sst_place_kernel(const uint8_t* raw, const uint64_t* raw_off,
                                                         const uint8_t* comp, const uint64_t* comp_off,
                                                         uint64_t comp_stride, const uint64_t* hoff,
                                                         const uint32_t* hsize, const uint8_t* type,
-                                                        uint8_t* file) {
+                                                        uint8_t* file, uint64_t cap) {
   const uint32_t b = blockIdx.x, t = threadIdx.x;
   const uint32_t ty = type[b];
+  const uint32_t n = hsize[b];
+  if (hoff[b] > cap || cap - hoff[b] < uint64_t{n} + 5u) return;
   const uint8_t* src =
       ty ? comp + (comp_off ? comp_off[b] : b * comp_stride) : raw + raw_off[b];
   uint8_t* dst = file + hoff[b];
-  const uint32_t n = hsize[b];
   for (uint32_t k = t; k < n; k += 256) dst[k] = src[k];
   if (t == 0) dst[n] = static_cast<uint8_t>(ty);
 }
@@ -861,13 +843,17 @@ SstWriteScratch sst_scratch_ragged(uint8_t* scratch, uint64_t scratch_bytes, uin
 // The pipeline: the slots scan (where the scratch has per-block offsets), the
 // codec, the status merge (where a status is asked for), the layout, the
 // place. An empty batch runs the layout alone, which stores end = file_offset.
+// dest (may be null): the base offset on the device and a bound on the file.
 hipError_t launch_sst_write_blocks(const uint8_t* raw, const uint64_t* raw_off,
                                    const uint32_t* raw_len, uint32_t nblocks, int compression,
                                    uint32_t max_len, const SstWriteScratch& s, uint8_t* file,
                                    uint64_t file_offset, uint64_t* hoff, uint32_t* hsize,
                                    uint8_t* type, uint64_t* end, int zstd_level, uint8_t* status,
-                                   hipStream_t stream) {
+                                   hipStream_t stream, const SstWriteDest* dest) {
   const bool any = nblocks != 0;
+  const uint64_t* base = dest != nullptr ? dest->base : nullptr;
+  const uint64_t cap = dest != nullptr ? dest->cap : ~uint64_t{0};
+  uint32_t* nfit = dest != nullptr ? dest->nfit : nullptr;
   if (any && compression != 0) {
     if (s.slot_off != nullptr)
       hipLaunchKernelGGL(sst_slots_kernel, dim3(1), dim3(1024), 0, stream, raw_len, nblocks,
@@ -890,10 +876,10 @@ hipError_t launch_sst_write_blocks(const uint8_t* raw, const uint64_t* raw_off,
                        s.cst, s.noroom, nblocks, status);
   hipLaunchKernelGGL(sst_layout_kernel, dim3(1), dim3(1024), 0, stream, raw_len, s.clen, s.cst,
                      nblocks, file_offset, hoff, hsize, type, end,
-                     static_cast<uint32_t>(compression == 2 ? 2 : 1));
+                     static_cast<uint32_t>(compression == 2 ? 2 : 1), base, cap, nfit);
   if (any)
     hipLaunchKernelGGL(sst_place_kernel, dim3(nblocks), dim3(256), 0, stream, raw, raw_off,
-                       s.slots, s.slot_off, s.stride, hoff, hsize, type, file);
+                       s.slots, s.slot_off, s.stride, hoff, hsize, type, file, cap);
   return hipGetLastError();
 }
 
