@@ -528,14 +528,26 @@ def _packed_offsets(torch, sizes, device):
     return off
 
 
-def snappy_compress(src, offsets, lengths, *, max_len: Optional[int] = None, dst=None,
-                    dst_offsets=None, stream=None):
-    """Batched port::Snappy_Compress (port/port_stdcxx.h:90-106) of block
-    i = src[offsets[i] : offsets[i] + lengths[i]]: snappy 1.1.8's bytes.
+def _snappy_bound(lens):
+    """snappy::MaxCompressedLength of each of an int64 tensor's lengths."""
+    return 32 + lens + lens // 6
 
-    Without dst, every block gets MaxCompressedLength bytes, packed. Returns
-    (dst uint8, dst_offsets int64, compressed lengths int32, status uint8:
-    SNAPPY_OK or SNAPPY_TOO_LARGE for a block longer than max_len)."""
+
+def _device_call(fn_name, dev, stream, *args, report: Optional[str] = None):
+    """One C-ABI call on dev's stream (the call's last argument); a failure is
+    raised under the name `report` (default: the function's own)."""
+    with _torch().cuda.device(dev):
+        rc = getattr(_lib, fn_name)(*args, _stream_handle(stream, dev))
+    _check(report or fn_name, rc)
+
+
+def _compress_outputs(src, offsets, lengths, max_len, dst, dst_offsets, bound, floor):
+    """What the three compressors share before their call: the length check,
+    the default max_len, a packed dst of bound(lengths) bytes a block (at
+    least `floor` bytes in all) unless one is given, the outputs. Returns
+    (max_len, (dst, dst_offsets, out_len, status), the call's first eight
+    arguments -- None for an empty batch, which makes no call). Every tensor
+    those point at is the caller's or among the outputs: it outlives the call."""
     torch = _torch()
     n = offsets.numel()
     dev = src.device
@@ -544,57 +556,47 @@ def snappy_compress(src, offsets, lengths, *, max_len: Optional[int] = None, dst
     if max_len is None:
         max_len = int(lengths.max().item()) if n else 0
     if dst is None:
-        lens = lengths.to(torch.int64)
-        room = 32 + lens + lens // 6
+        room = bound(lengths.to(torch.int64))
         dst_offsets = _packed_offsets(torch, room, dev)
-        dst = torch.empty(int(room.sum().item()) if n else 0, dtype=torch.uint8, device=dev)
+        dst = torch.empty(max(floor, int(room.sum().item())) if n else floor, dtype=torch.uint8,
+                          device=dev)
     elif dst_offsets is None:
         raise ValueError("dst needs dst_offsets")
     out_len = torch.empty(n, dtype=torch.int32, device=dev)
     status = torch.empty(n, dtype=torch.uint8, device=dev)
+    args = None
     if n:
-        with torch.cuda.device(dev):
-            rc = _lib.lvkv_snappy_compress_device(
-                _dev_ptr(src, "src", (torch.uint8, torch.int8)),
+        args = [_dev_ptr(src, "src", (torch.uint8, torch.int8)),
                 _dev_ptr(offsets, "offsets", (torch.int64,)),
                 _dev_ptr(lengths, "lengths", (torch.int32,)),
                 _dev_ptr(dst, "dst", (torch.uint8, torch.int8)),
                 _dev_ptr(dst_offsets, "dst_offsets", (torch.int64,), n),
-                _dev_ptr(out_len, "out_len"), _dev_ptr(status, "status"), n,
-                max(0, min(int(max_len), 0xFFFFFFFF)), _stream_handle(stream, dev))
-        _check("lvkv_snappy_compress_device", rc)
-    return dst, dst_offsets, out_len, status
+                _dev_ptr(out_len, "out_len"), _dev_ptr(status, "status"), n]
+    return max_len, (dst, dst_offsets, out_len, status), args
 
 
-def snappy_uncompressed_length(src, offsets, lengths, *, stream=None):
-    """Batched port::Snappy_GetUncompressedLength (port/port_stdcxx.h:108-119).
-    Returns (lengths int32 as u32 bit patterns, status uint8: SNAPPY_OK /
-    SNAPPY_BAD_LENGTH)."""
+def _ulen_call(fn_name, src, offsets, lengths, stream):
+    """Both codecs' GetUncompressedLength: (lengths int32, status uint8)."""
     torch = _torch()
     n = offsets.numel()
     dev = src.device
     ulen = torch.zeros(n, dtype=torch.int32, device=dev)
     status = torch.empty(n, dtype=torch.uint8, device=dev)
     if n:
-        with torch.cuda.device(dev):
-            rc = _lib.lvkv_snappy_uncompressed_length_device(
-                _dev_ptr(src, "src", (torch.uint8, torch.int8)),
-                _dev_ptr(offsets, "offsets", (torch.int64,)),
-                _dev_ptr(lengths, "lengths", (torch.int32,), n),
-                _dev_ptr(ulen, "ulen"), _dev_ptr(status, "status"), n,
-                _stream_handle(stream, dev))
-        _check("lvkv_snappy_uncompressed_length_device", rc)
+        _device_call(fn_name, dev, stream,
+                     _dev_ptr(src, "src", (torch.uint8, torch.int8)),
+                     _dev_ptr(offsets, "offsets", (torch.int64,)),
+                     _dev_ptr(lengths, "lengths", (torch.int32,), n),
+                     _dev_ptr(ulen, "ulen"), _dev_ptr(status, "status"), n)
     return ulen, status
 
 
-def snappy_uncompress(src, offsets, lengths, *, max_ulen: int, dst=None, dst_offsets=None,
-                      dst_caps=None, stream=None):
-    """Batched port::Snappy_Uncompress (port/port_stdcxx.h:121-133) as
-    ReadBlock runs it (table/format.cc:120-135). Without dst, every stream
-    gets max_ulen bytes. max_ulen sizes the LDS staging; a longer stream is
-    decoded from HBM by the call's second kernel. Returns (dst uint8,
-    dst_offsets int64, uncompressed lengths int32, status uint8: SNAPPY_OK /
-    BAD_LENGTH / BAD_CONTENTS / CAPACITY)."""
+def _uncompress_call(fn_name, src, offsets, lengths, max_ulen, dst, dst_offsets, dst_caps, stream,
+                     *extra, report=None):
+    """Both decoders: the bound on max_ulen, a dst of max_ulen bytes a stream
+    unless one is given, the outputs, the call (`extra`: the debug entry's
+    arguments between status and n; made here, while the default dst_caps is
+    alive). Returns (dst, dst_offsets, out_len, status)."""
     torch = _torch()
     n = offsets.numel()
     dev = src.device
@@ -609,18 +611,51 @@ def snappy_uncompress(src, offsets, lengths, *, max_ulen: int, dst=None, dst_off
     out_len = torch.zeros(n, dtype=torch.int32, device=dev)
     status = torch.empty(n, dtype=torch.uint8, device=dev)
     if n:
-        with torch.cuda.device(dev):
-            rc = _lib.lvkv_snappy_uncompress_device(
-                _dev_ptr(src, "src", (torch.uint8, torch.int8)),
-                _dev_ptr(offsets, "offsets", (torch.int64,)),
-                _dev_ptr(lengths, "lengths", (torch.int32,), n),
-                _dev_ptr(dst, "dst", (torch.uint8, torch.int8)),
-                _dev_ptr(dst_offsets, "dst_offsets", (torch.int64,), n),
-                _dev_ptr(dst_caps, "dst_caps", (torch.int32,), n),
-                _dev_ptr(out_len, "out_len"), _dev_ptr(status, "status"), n, max_ulen,
-                _stream_handle(stream, dev))
-        _check("lvkv_snappy_uncompress_device", rc)
+        _device_call(fn_name, dev, stream,
+                     _dev_ptr(src, "src", (torch.uint8, torch.int8)),
+                     _dev_ptr(offsets, "offsets", (torch.int64,)),
+                     _dev_ptr(lengths, "lengths", (torch.int32,), n),
+                     _dev_ptr(dst, "dst", (torch.uint8, torch.int8)),
+                     _dev_ptr(dst_offsets, "dst_offsets", (torch.int64,), n),
+                     _dev_ptr(dst_caps, "dst_caps", (torch.int32,), n),
+                     _dev_ptr(out_len, "out_len"), _dev_ptr(status, "status"), *extra, n, max_ulen,
+                     report=report)
     return dst, dst_offsets, out_len, status
+
+
+def snappy_compress(src, offsets, lengths, *, max_len: Optional[int] = None, dst=None,
+                    dst_offsets=None, stream=None):
+    """Batched port::Snappy_Compress (port/port_stdcxx.h:90-106) of block
+    i = src[offsets[i] : offsets[i] + lengths[i]]: snappy 1.1.8's bytes.
+
+    Without dst, every block gets MaxCompressedLength bytes, packed. Returns
+    (dst uint8, dst_offsets int64, compressed lengths int32, status uint8:
+    SNAPPY_OK or SNAPPY_TOO_LARGE for a block longer than max_len)."""
+    max_len, outs, args = _compress_outputs(src, offsets, lengths, max_len, dst, dst_offsets,
+                                            _snappy_bound, 0)
+    if args:
+        _device_call("lvkv_snappy_compress_device", src.device, stream, *args,
+                     max(0, min(int(max_len), 0xFFFFFFFF)))
+    return outs
+
+
+def snappy_uncompressed_length(src, offsets, lengths, *, stream=None):
+    """Batched port::Snappy_GetUncompressedLength (port/port_stdcxx.h:108-119).
+    Returns (lengths int32 as u32 bit patterns, status uint8: SNAPPY_OK /
+    SNAPPY_BAD_LENGTH)."""
+    return _ulen_call("lvkv_snappy_uncompressed_length_device", src, offsets, lengths, stream)
+
+
+def snappy_uncompress(src, offsets, lengths, *, max_ulen: int, dst=None, dst_offsets=None,
+                      dst_caps=None, stream=None):
+    """Batched port::Snappy_Uncompress (port/port_stdcxx.h:121-133) as
+    ReadBlock runs it (table/format.cc:120-135). Without dst, every stream
+    gets max_ulen bytes. max_ulen sizes the LDS staging; a longer stream is
+    decoded from HBM by the call's second kernel. Returns (dst uint8,
+    dst_offsets int64, uncompressed lengths int32, status uint8: SNAPPY_OK /
+    BAD_LENGTH / BAD_CONTENTS / CAPACITY)."""
+    return _uncompress_call("lvkv_snappy_uncompress_device", src, offsets, lengths, max_ulen, dst,
+                            dst_offsets, dst_caps, stream)
 
 
 ZSTD_OK, ZSTD_BAD_LENGTH, ZSTD_BAD_CONTENTS, ZSTD_CAPACITY, ZSTD_TOO_LARGE, \
@@ -634,6 +669,11 @@ def zstd_compress_bound(n: int) -> int:
     return int(_lib.lvkv_zstd_compress_bound(n))
 
 
+def _zstd_bound(lens):
+    """ZSTD_compressBound of each of an int64 tensor's lengths."""
+    return lens + (lens >> 8) + _torch().clamp((131072 - lens) >> 11, min=0)
+
+
 def zstd_compress(src, offsets, lengths, *, level: int = 1, max_len: Optional[int] = None,
                   dst=None, dst_offsets=None, stream=None):
     """Batched port::Zstd_Compress(level, block) (port/port_stdcxx.h:133-161) of
@@ -642,36 +682,13 @@ def zstd_compress(src, offsets, lengths, *, level: int = 1, max_len: Optional[in
     setCParams. Without dst, every block gets ZSTD_compressBound bytes,
     packed. Returns (dst uint8, dst_offsets int64, frame lengths int32,
     status uint8: ZSTD_OK / ZSTD_TOO_LARGE / ZSTD_UNSUPPORTED)."""
-    torch = _torch()
-    n = offsets.numel()
-    dev = src.device
-    if lengths.numel() != n:
-        raise ValueError("offsets and lengths differ in length")
-    if max_len is None:
-        max_len = int(lengths.max().item()) if n else 0
     # (max_len past ZSTD_COMPRESS_MAX_BLOCK: the C-ABI's LVKV_ERR_INVALID)
-    if dst is None:
-        lens = lengths.to(torch.int64)
-        room = lens + (lens >> 8) + torch.clamp((131072 - lens) >> 11, min=0)
-        dst_offsets = _packed_offsets(torch, room, dev)
-        dst = torch.empty(max(1, int(room.sum().item())) if n else 1, dtype=torch.uint8,
-                          device=dev)
-    elif dst_offsets is None:
-        raise ValueError("dst needs dst_offsets")
-    out_len = torch.empty(n, dtype=torch.int32, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    if n:
-        with torch.cuda.device(dev):
-            rc = _lib.lvkv_zstd_compress_device(
-                _dev_ptr(src, "src", (torch.uint8, torch.int8)),
-                _dev_ptr(offsets, "offsets", (torch.int64,)),
-                _dev_ptr(lengths, "lengths", (torch.int32,)),
-                _dev_ptr(dst, "dst", (torch.uint8, torch.int8)),
-                _dev_ptr(dst_offsets, "dst_offsets", (torch.int64,), n),
-                _dev_ptr(out_len, "out_len"), _dev_ptr(status, "status"), n, int(max_len),
-                int(level), _stream_handle(stream, dev))
-        _check("lvkv_zstd_compress_device", rc)
-    return dst, dst_offsets, out_len, status
+    max_len, outs, args = _compress_outputs(src, offsets, lengths, max_len, dst, dst_offsets,
+                                            _zstd_bound, 1)
+    if args:
+        _device_call("lvkv_zstd_compress_device", src.device, stream, *args, int(max_len),
+                     int(level))
+    return outs
 
 
 ZSTD_COMPRESS_BIG_MAX_BLOCK = 131072
@@ -696,40 +713,19 @@ def zstd_compress_big(src, offsets, lengths, *, level: int = 1, max_len: Optiona
     bytes; it belongs to the call until the stream has run it). Returns the
     same 4-tuple as zstd_compress."""
     torch = _torch()
-    n = offsets.numel()
-    dev = src.device
-    if lengths.numel() != n:
-        raise ValueError("offsets and lengths differ in length")
-    if max_len is None:
-        max_len = int(lengths.max().item()) if n else 0
+    max_len, outs, args = _compress_outputs(src, offsets, lengths, max_len, dst, dst_offsets,
+                                            _zstd_bound, 1)
     max_len = max(0, min(int(max_len), 0xFFFFFFFF))
-    if dst is None:
-        lens = lengths.to(torch.int64)
-        room = lens + (lens >> 8) + torch.clamp((131072 - lens) >> 11, min=0)
-        dst_offsets = _packed_offsets(torch, room, dev)
-        dst = torch.empty(max(1, int(room.sum().item())) if n else 1, dtype=torch.uint8,
-                          device=dev)
-    elif dst_offsets is None:
-        raise ValueError("dst needs dst_offsets")
-    out_len = torch.empty(n, dtype=torch.int32, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    if n:
+    if args:
+        dev = src.device
         need = zstd_compress_big_scratch_bytes(max_len)
         if scratch is None and need:
             scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lvkv_zstd_compress_big_device(
-                _dev_ptr(src, "src", (torch.uint8, torch.int8)),
-                _dev_ptr(offsets, "offsets", (torch.int64,)),
-                _dev_ptr(lengths, "lengths", (torch.int32,)),
-                _dev_ptr(dst, "dst", (torch.uint8, torch.int8)),
-                _dev_ptr(dst_offsets, "dst_offsets", (torch.int64,), n),
-                _dev_ptr(out_len, "out_len"), _dev_ptr(status, "status"), n, max_len, int(level),
-                _dev_ptr(scratch, "scratch", (torch.uint8, torch.int8))
-                if scratch is not None else None,
-                scratch.numel() if scratch is not None else 0, _stream_handle(stream, dev))
-        _check("lvkv_zstd_compress_big_device", rc)
-    return dst, dst_offsets, out_len, status
+        _device_call("lvkv_zstd_compress_big_device", dev, stream, *args, max_len, int(level),
+                     _dev_ptr(scratch, "scratch", (torch.uint8, torch.int8))
+                     if scratch is not None else None,
+                     scratch.numel() if scratch is not None else 0)
+    return outs
 
 
 READ_OK, READ_CHECKSUM, READ_BAD_TYPE, READ_SNAPPY_LENGTH, READ_SNAPPY_CONTENTS, \
@@ -740,21 +736,7 @@ def zstd_uncompressed_length(src, offsets, lengths, *, stream=None):
     """Batched port::Zstd_GetUncompressedLength (port/port_stdcxx.h:163-177):
     (lengths int32 as u32, status uint8: SNAPPY_OK / SNAPPY_BAD_LENGTH (0) /
     SNAPPY_TOO_LARGE (unknown, malformed, > 32 bits))."""
-    torch = _torch()
-    n = offsets.numel()
-    dev = src.device
-    ulen = torch.zeros(n, dtype=torch.int32, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    if n:
-        with torch.cuda.device(dev):
-            rc = _lib.lvkv_zstd_uncompressed_length_device(
-                _dev_ptr(src, "src", (torch.uint8, torch.int8)),
-                _dev_ptr(offsets, "offsets", (torch.int64,)),
-                _dev_ptr(lengths, "lengths", (torch.int32,), n),
-                _dev_ptr(ulen, "ulen"), _dev_ptr(status, "status"), n,
-                _stream_handle(stream, dev))
-        _check("lvkv_zstd_uncompressed_length_device", rc)
-    return ulen, status
+    return _ulen_call("lvkv_zstd_uncompressed_length_device", src, offsets, lengths, stream)
 
 
 def zstd_uncompress(src, offsets, lengths, *, max_ulen: int, dst=None, dst_offsets=None,
@@ -762,39 +744,14 @@ def zstd_uncompress(src, offsets, lengths, *, max_ulen: int, dst=None, dst_offse
     """Batched port::Zstd_Uncompress (port/port_stdcxx.h:179-199) as ReadBlock
     runs it (table/format.cc:138-155). Statuses as snappy_uncompress. With
     detail=True also returns the failure site per stream (a debug hook)."""
+    if not detail:
+        return _uncompress_call("lvkv_zstd_uncompress_device", src, offsets, lengths, max_ulen, dst,
+                                dst_offsets, dst_caps, stream)
     torch = _torch()
-    n = offsets.numel()
-    dev = src.device
-    if not 0 <= max_ulen <= SNAPPY_MAX_BLOCK:
-        raise ValueError(f"max_ulen must be in [0, {SNAPPY_MAX_BLOCK}]")
-    if dst is None:
-        dst_caps = torch.full((n,), max_ulen, dtype=torch.int32, device=dev)
-        dst_offsets = torch.arange(n, dtype=torch.int64, device=dev) * max_ulen
-        dst = torch.empty(max(1, n * max_ulen), dtype=torch.uint8, device=dev)
-    elif dst_offsets is None or dst_caps is None:
-        raise ValueError("dst needs dst_offsets and dst_caps")
-    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    status = torch.empty(n, dtype=torch.uint8, device=dev)
-    why = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
-    if n:
-        args = [_dev_ptr(src, "src", (torch.uint8, torch.int8)),
-                _dev_ptr(offsets, "offsets", (torch.int64,)),
-                _dev_ptr(lengths, "lengths", (torch.int32,), n),
-                _dev_ptr(dst, "dst", (torch.uint8, torch.int8)),
-                _dev_ptr(dst_offsets, "dst_offsets", (torch.int64,), n),
-                _dev_ptr(dst_caps, "dst_caps", (torch.int32,), n),
-                _dev_ptr(out_len, "out_len"), _dev_ptr(status, "status")]
-        with torch.cuda.device(dev):
-            if detail:
-                rc = _lib.lvkv_debug_zstd_uncompress_device(*args, _dev_ptr(why, "detail"), n,
-                                                            max_ulen, _stream_handle(stream, dev))
-            else:
-                rc = _lib.lvkv_zstd_uncompress_device(*args, n, max_ulen,
-                                                      _stream_handle(stream, dev))
-        _check("lvkv_zstd_uncompress_device", rc)
-    if detail:
-        return dst, dst_offsets, out_len, status, why
-    return dst, dst_offsets, out_len, status
+    why = torch.zeros(max(1, offsets.numel()), dtype=torch.int32, device=src.device)
+    return _uncompress_call("lvkv_debug_zstd_uncompress_device", src, offsets, lengths, max_ulen,
+                            dst, dst_offsets, dst_caps, stream, _dev_ptr(why, "detail"),
+                            report="lvkv_zstd_uncompress_device") + (why,)
 
 
 def _sst_write(raw, offsets, lengths, compression, zstd_level, max_len, file, file_offset, stream,

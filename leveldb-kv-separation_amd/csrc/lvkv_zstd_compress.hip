@@ -30,9 +30,11 @@
 // and the three interleaved FSE state chains.
 //
 // Blocks past that LDS plan, up to one Zstd block (128 KiB), are a second
-// kernel's (zstd_compress_big_kernel, below): the same code on
-// a block kept in an HBM scratch slot, the hash table and the frame's body
-// in LDS.
+// kernel's (zstd_compress_big_kernel, below): the same
+// match_block and the same block_body on a block kept in an HBM scratch slot,
+// the hash table and the frame's body in LDS. The two homes differ in the
+// sequence store (Seqs / SeqsBig: packing, register window, fence) and in
+// where ZcBlock puts the codes and takes a raw block's bytes from.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -60,6 +62,22 @@ __device__ __forceinline__ void lds_sync() {
   asm volatile("" ::: "memory");
 #endif
 }
+// Everything this wave wrote to HBM is visible to its later reads (other
+// lanes' included): the HBM-side counterpart of lds_sync().
+__device__ __forceinline__ void hbm_sync() {
+  __threadfence();
+  lds_sync();
+}
+
+// the wave's largest v, in every lane
+template <typename T>
+__device__ __forceinline__ T wave_max(T v) {
+  for (uint32_t dd = 32; dd >= 1; dd >>= 1) {
+    const T o = __shfl_xor(v, dd);
+    v = o > v ? o : v;
+  }
+  return v;
+}
 
 __host__ __device__ __forceinline__ uint32_t hibit(uint32_t v) { return 31u - __builtin_clz(v); }
 
@@ -75,17 +93,24 @@ __device__ __forceinline__ uint64_t ld64(const uint8_t* b, uint32_t p) {
   return (static_cast<uint64_t>(hi) << 32) | lo;
 }
 
-__device__ __forceinline__ void stage(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t pad,
-                                      uint32_t lane) {
+// The block's copy: dst[0, n) = src[0, n), then 16 zero bytes (up to the
+// dword). dst is dword-aligned; src is read in aligned dwords that hold at
+// least one byte of the block, and no byte past the block reaches dst.
+__device__ __forceinline__ void stage(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
   const uint32_t mis = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(src)) & 3u;
   const uint32_t* s = reinterpret_cast<const uint32_t*>(src - mis);
-  const uint32_t nd = (n + 3u) >> 2;
-  for (uint32_t i = lane; i < nd; i += 64) {
-    const uint32_t lo = s[i];
-    const uint32_t hi = (mis != 0 && 4u * (i + 1u) < mis + n) ? s[i + 1] : 0u;
-    reinterpret_cast<uint32_t*>(dst)[i] = __builtin_amdgcn_alignbyte(hi, lo, mis);
+  const uint32_t nd = (n + 3u) >> 2, ndp = (n + 16u + 3u) >> 2;
+  for (uint32_t i = lane; i < ndp; i += 64) {
+    uint32_t v = 0;
+    if (i < nd) {
+      const uint32_t lo = s[i];
+      const uint32_t hi = (mis != 0 && 4u * (i + 1u) < mis + n) ? s[i + 1] : 0u;
+      v = __builtin_amdgcn_alignbyte(hi, lo, mis);
+      const uint32_t rem = n - 4u * i;
+      if (rem < 4u) v &= (1u << (8u * rem)) - 1u;
+    }
+    reinterpret_cast<uint32_t*>(dst)[i] = v;
   }
-  for (uint32_t i = n + lane; i < n + pad; i += 64) dst[i] = 0;
 }
 
 // ---- parameters (ZSTD_getCParams + ZSTD_adjustCParams, 1.4.9) -------------
@@ -322,12 +347,7 @@ __device__ __forceinline__ int32_t fse_normalize(uint32_t cnt, uint32_t tl, uint
   for (uint32_t dd = 32; dd >= 1; dd >>= 1) sum += __shfl_xor(sum, dd);
   const int32_t still = (1 << tl) - static_cast<int32_t>(uni(static_cast<uint32_t>(sum)));
   // the first symbol of the largest share (strictly larger replaces)
-  int32_t best = big ? p : 0;
-  for (uint32_t dd = 32; dd >= 1; dd >>= 1) {
-    const int32_t o = __shfl_xor(best, dd);
-    best = o > best ? o : best;
-  }
-  const int32_t largest_p = static_cast<int32_t>(uni(static_cast<uint32_t>(best)));
+  const int32_t largest_p = static_cast<int32_t>(uni(static_cast<uint32_t>(wave_max(big ? p : 0))));
   const uint64_t lm = __ballot(big && p == largest_p && largest_p > 0);
   const uint32_t largest = lm ? static_cast<uint32_t>(__builtin_ctzll(lm)) : 0u;
   const int32_t nl = static_cast<int32_t>(uni(__builtin_amdgcn_readlane(static_cast<uint32_t>(p), largest)));
@@ -373,12 +393,7 @@ __device__ __forceinline__ int32_t fse_normalize(uint32_t cnt, uint32_t tl, uint
       to_dist = (1u << tl) - distributed;
     }
     if (distributed == max_sym + 1u) {
-      uint32_t mc = lane <= max_sym ? cnt : 0u;
-      for (uint32_t dd = 32; dd >= 1; dd >>= 1) {
-        const uint32_t o = __shfl_xor(mc, dd);
-        mc = o > mc ? o : mc;
-      }
-      mc = uni(mc);
+      const uint32_t mc = uni(wave_max(lane <= max_sym ? cnt : 0u));
       const uint64_t m = __ballot(lane <= max_sym && cnt == mc && mc > 0);
       const uint32_t mv = m ? static_cast<uint32_t>(__builtin_ctzll(m)) : 0u;
       if (lane == mv) q += static_cast<int32_t>(to_dist);
@@ -673,14 +688,6 @@ __device__ __forceinline__ uint32_t rd256(const uint32_t (&a)[4], uint32_t i) {
   const uint32_t v = g == 0 ? a[0] : (g == 1 ? a[1] : (g == 2 ? a[2] : a[3]));
   return __builtin_amdgcn_readlane(v, i & 63u);
 }
-__device__ __forceinline__ void wr256(uint32_t (&a)[4], uint32_t i, uint32_t v) {
-  const uint32_t g = i >> 6, l = i & 63u;
-  const bool me = threadIdx.x == l;  // (v_cmp + v_cndmask: a lane write)
-  a[0] = (g == 0 && me) ? v : a[0];
-  a[1] = (g == 1 && me) ? v : a[1];
-  a[2] = (g == 2 && me) ? v : a[2];
-  a[3] = (g == 3 && me) ? v : a[3];
-}
 // lane-varying gather from a 256-entry register array
 __device__ __forceinline__ uint32_t gather256(const uint32_t (&a)[4], uint32_t i) {
   const int addr = static_cast<int>((i & 63u) << 2);
@@ -928,44 +935,37 @@ __device__ __forceinline__ uint32_t huf_build(const uint32_t (&c)[4], uint32_t m
 
 // ---- the literals section (ZSTD_compressLiterals) ---------------------------
 
-__device__ __forceinline__ uint32_t raw_literals(uint8_t* out, const uint8_t* lits, uint32_t n, uint32_t lane) {
+// The header of a raw (type 0) or RLE (type 1) literals section of n bytes,
+// by lane 0: its size.
+__device__ __forceinline__ uint32_t lit_header(uint8_t* out, uint32_t type, uint32_t n, uint32_t lane) {
   const uint32_t fl = 1u + (n > 31) + (n > 4095);
   if (lane == 0) {
     if (fl == 1) {
-      out[0] = static_cast<uint8_t>(n << 3);
+      out[0] = static_cast<uint8_t>(type + (n << 3));
     } else if (fl == 2) {
-      const uint32_t h = (1u << 2) + (n << 4);
+      const uint32_t h = type + (1u << 2) + (n << 4);
       out[0] = static_cast<uint8_t>(h);
       out[1] = static_cast<uint8_t>(h >> 8);
     } else {
-      const uint32_t h = (3u << 2) + (n << 4);
+      const uint32_t h = type + (3u << 2) + (n << 4);
       out[0] = static_cast<uint8_t>(h);
       out[1] = static_cast<uint8_t>(h >> 8);
       out[2] = static_cast<uint8_t>(h >> 16);
     }
   }
+  return fl;
+}
+
+__device__ __forceinline__ uint32_t raw_literals(uint8_t* out, const uint8_t* lits, uint32_t n, uint32_t lane) {
+  const uint32_t fl = lit_header(out, 0, n, lane);
   for (uint32_t k = lane; k < n; k += 64) out[fl + k] = lits[k];
   lds_sync();
   return fl + n;
 }
 
 __device__ __forceinline__ uint32_t rle_literals(uint8_t* out, const uint8_t* lits, uint32_t n, uint32_t lane) {
-  const uint32_t fl = 1u + (n > 31) + (n > 4095);
-  if (lane == 0) {
-    if (fl == 1) {
-      out[0] = static_cast<uint8_t>(1u + (n << 3));
-    } else if (fl == 2) {
-      const uint32_t h = 1u + (1u << 2) + (n << 4);
-      out[0] = static_cast<uint8_t>(h);
-      out[1] = static_cast<uint8_t>(h >> 8);
-    } else {
-      const uint32_t h = 1u + (3u << 2) + (n << 4);
-      out[0] = static_cast<uint8_t>(h);
-      out[1] = static_cast<uint8_t>(h >> 8);
-      out[2] = static_cast<uint8_t>(h >> 16);
-    }
-    out[fl] = lits[0];
-  }
+  const uint32_t fl = lit_header(out, 1, n, lane);
+  if (lane == 0) out[fl] = lits[0];
   lds_sync();
   return fl + 1u;
 }
@@ -1029,12 +1029,7 @@ __device__ __forceinline__ uint32_t huf_compress_weights(const uint32_t (&w)[4],
   }
   const uint64_t nzm = __ballot(lane < 13 && cnt != 0);
   const uint32_t max_sym = 63u - __builtin_clzll(nzm);
-  uint32_t mc = cnt;
-  for (uint32_t dd = 32; dd >= 1; dd >>= 1) {
-    const uint32_t o = __shfl_xor(mc, dd);
-    mc = o > mc ? o : mc;
-  }
-  mc = uni(mc);
+  const uint32_t mc = uni(wave_max(cnt));
   if (mc == nw || mc == 1) return 0;
   const uint32_t tl = fse_opt_log(6, nw, max_sym, 2);
   const int32_t normv = fse_normalize(cnt, tl, nw, max_sym, false, lane);
@@ -1059,12 +1054,7 @@ __device__ __forceinline__ uint32_t huf_compress_weights(const uint32_t (&w)[4],
   // chain B the others, each from its highest index down; emission step e
   // (e = 0..nw-3) encodes index nw - 3 - e: chain A's on even e. A is s1
   // when nw is odd, s2 when it is even.
-  auto wat = [&](uint32_t i) -> uint32_t {
-    const uint32_t g = i >> 6, l = i & 63u;
-    const uint32_t v = g == 0 ? w[0] : (g == 1 ? w[1] : (g == 2 ? w[2] : w[3]));
-    return uni(__builtin_amdgcn_readlane(v, l));
-  };
-  uint32_t sa = fse_init(t, wat(nw - 1u)), sb = fse_init(t, wat(nw - 2u));
+  uint32_t sa = fse_init(t, uni(rd256(w, nw - 1u))), sb = fse_init(t, uni(rd256(w, nw - 2u)));
   const bool odd = (nw & 1u) != 0;
   const uint32_t E = nw - 2u;
   // per step, in parallel: its symbol's (deltaNbBits, deltaFindState)
@@ -1140,11 +1130,7 @@ __device__ __forceinline__ uint32_t compress_literals(uint8_t* out, const uint8_
     largest = c[g] > largest ? c[g] : largest;
     nzm[g] = __ballot(c[g] != 0);
   }
-  for (uint32_t dd = 32; dd >= 1; dd >>= 1) {
-    const uint32_t o = __shfl_xor(largest, dd);
-    largest = o > largest ? o : largest;
-  }
-  largest = uni(largest);
+  largest = uni(wave_max(largest));
   uint32_t max_sym = 0;
 #pragma unroll
   for (uint32_t g = 0; g < 4; ++g)
@@ -1334,12 +1320,7 @@ __device__ __forceinline__ uint32_t seq_table(uint32_t table, const uint8_t* cod
   uint32_t c = lane <= mx ? cnt[lane] : 0u;
   const uint64_t nz = __ballot(c != 0);
   const uint32_t max_sym = 63u - __builtin_clzll(nz);
-  uint32_t most = c;
-  for (uint32_t dd = 32; dd >= 1; dd >>= 1) {
-    const uint32_t o = __shfl_xor(most, dd);
-    most = o > most ? o : most;
-  }
-  most = uni(most);
+  const uint32_t most = uni(wave_max(c));
   const uint32_t dlog = table == 1 ? 5u : 6u;
   const bool allowed = table == 1 ? max_sym <= 28u : true;
   const uint32_t type = select_type(most, nbseq, dlog, allowed);
@@ -1471,23 +1452,42 @@ __device__ __forceinline__ uint32_t zcount(const uint8_t* in, uint32_t a, uint32
   }
 }
 
+// A block's literals and sequences. The two stores (blocks the LDS plan holds;
+// longer ones) differ in how a sequence is packed (put, unpack, and Window:
+// 64 sequences in registers, lane k sequence base + k, read by the serial
+// coder with v_readlane) and in the fence that orders the wave's writes to
+// where the store and its codes live (sync).
 struct Seqs {
   uint8_t* lits;  // the match finder's: the block's frame slot in HBM (kLitStage)
   uint32_t* sll;  // litLength | mlBase << 16
   uint16_t* sof;  // offset code + 1 (<= max_len + 3)
   uint32_t nlit, nseq;
-};
 
-__device__ __forceinline__ void store_seq(Seqs& s, const uint8_t* in, uint32_t anchor, uint32_t litlen,
-                                          uint32_t offcode, uint32_t mlbase, uint32_t lane) {
-  for (uint32_t k = lane; k < litlen; k += 64) s.lits[s.nlit + k] = in[anchor + k];
-  if (lane == 0) {
-    s.sll[s.nseq] = litlen | (mlbase << 16);
-    s.sof[s.nseq] = static_cast<uint16_t>(offcode + 1u);
+  __device__ __forceinline__ void put(uint32_t k, uint32_t litlen, uint32_t offcode, uint32_t mlbase) {
+    sll[k] = litlen | (mlbase << 16);
+    sof[k] = static_cast<uint16_t>(offcode + 1u);
   }
-  s.nlit += litlen;
-  s.nseq += 1u;
-}
+  __device__ __forceinline__ void unpack(uint32_t k, uint32_t* ll, uint32_t* mlb, uint32_t* of) const {
+    const uint32_t v = sll[k];
+    *ll = v & 0xFFFFu;
+    *mlb = v >> 16;
+    *of = sof[k];
+  }
+  static __device__ __forceinline__ void sync() { lds_sync(); }
+  struct Window {  // the packed word in one VGPR, split after the readlane
+    uint32_t rv, ro;
+    __device__ __forceinline__ void load(const Seqs& s, uint32_t k) {
+      rv = k < s.nseq ? s.sll[k] : 0u;
+      ro = k < s.nseq ? s.sof[k] : 0u;
+    }
+    __device__ __forceinline__ void at(uint32_t j, uint32_t* ll, uint32_t* mlb, uint32_t* of) const {
+      const uint32_t v = __builtin_amdgcn_readlane(rv, j);
+      *ll = v & 0xFFFFu;
+      *mlb = v >> 16;
+      *of = __builtin_amdgcn_readlane(ro, j);
+    }
+  };
+};
 
 // The sequences of a block past the LDS plan (up to 128 KiB), in HBM: two
 // words a sequence -- litLength (17 bits) | the low 15 bits of mlBase << 17,
@@ -1501,15 +1501,38 @@ struct SeqsBig {
   uint8_t* lits;
   uint32_t* sq;
   uint32_t nlit, nseq;
+
+  __device__ __forceinline__ void put(uint32_t k, uint32_t litlen, uint32_t offcode, uint32_t mlbase) {
+    sq[2u * k] = litlen | (mlbase << 17);
+    sq[2u * k + 1u] = (offcode + 1u) | ((mlbase >> 15) << 18);
+  }
+  __device__ __forceinline__ void unpack(uint32_t k, uint32_t* ll, uint32_t* mlb, uint32_t* of) const {
+    const uint32_t w0 = sq[2u * k], w1 = sq[2u * k + 1u];
+    *ll = w0 & 0x1FFFFu;
+    *mlb = (w0 >> 17) | ((w1 >> 18) << 15);
+    *of = w1 & 0x3FFFFu;
+  }
+  static __device__ __forceinline__ void sync() { hbm_sync(); }
+  struct Window {  // unpacked at the load: three VGPRs
+    uint32_t rl, rm, ro;
+    __device__ __forceinline__ void load(const SeqsBig& s, uint32_t k) {
+      rl = rm = ro = 0;
+      if (k < s.nseq) s.unpack(k, &rl, &rm, &ro);
+    }
+    __device__ __forceinline__ void at(uint32_t j, uint32_t* ll, uint32_t* mlb, uint32_t* of) const {
+      *ll = __builtin_amdgcn_readlane(rl, j);
+      *mlb = __builtin_amdgcn_readlane(rm, j);
+      *of = __builtin_amdgcn_readlane(ro, j);
+    }
+  };
 };
 
-__device__ __forceinline__ void store_seq(SeqsBig& s, const uint8_t* in, uint32_t anchor, uint32_t litlen,
+// One sequence: its literals after the block's earlier ones, its record.
+template <typename Sq>
+__device__ __forceinline__ void store_seq(Sq& s, const uint8_t* in, uint32_t anchor, uint32_t litlen,
                                           uint32_t offcode, uint32_t mlbase, uint32_t lane) {
   for (uint32_t k = lane; k < litlen; k += 64) s.lits[s.nlit + k] = in[anchor + k];
-  if (lane == 0) {
-    s.sq[2u * s.nseq] = litlen | (mlbase << 17);
-    s.sq[2u * s.nseq + 1u] = (offcode + 1u) | ((mlbase >> 15) << 18);
-  }
+  if (lane == 0) s.put(s.nseq, litlen, offcode, mlbase);
   s.nlit += litlen;
   s.nseq += 1u;
 }
@@ -1522,7 +1545,6 @@ __device__ __forceinline__ void match_block(const uint8_t* in, uint32_t n, TIdx*
   const uint32_t hlog = zp.hlog, mls = zp.mls;
   const uint32_t ss = zp.tl + (zp.tl ? 0u : 1u) + 1u;
   const int32_t ilimit = static_cast<int32_t>(n) - 8;
-  const uint64_t below = (uint64_t{1} << lane) - 1u;
   uint32_t anchor = 0;
   uint32_t ip0 = 1;  // (istart == prefixStart: the first position is skipped)
   // repcodes 1, 4, 8; maxRep = 1 at ip0 = 1: offset_2 (4) is set aside
@@ -1725,7 +1747,158 @@ __device__ __forceinline__ void match_block(const uint8_t* in, uint32_t n, TIdx*
   for (uint32_t k = lane; k < n - anchor; k += 64) sq.lits[sq.nlit + k] = in[anchor + k];
   sq.nlit += n - anchor;
   lds_sync();
-  (void)below;
+}
+
+// One block's frame and the places its body is put together in (finish() and
+// raw_block() read the frame members only: g to status).
+struct ZcBlock {
+  uint8_t* g;          // the frame
+  uint32_t fh, n;      // its header's bytes, the block's
+  const uint8_t* raw;  // what a raw block is copied from
+  uint32_t* dst_len;   // the block's frame length and status
+  uint8_t* status;
+  uint8_t* out;        // the body (LDS, dword-aligned)
+  uint8_t* ent;        // the entropy scratch (LDS)
+  HNode* nodes;
+  uint8_t* llc;        // u8[3][round16(smax)]: LL, OF, ML codes (where the sequences live)
+  uint32_t smax;
+};
+
+__device__ __forceinline__ void finish(const ZcBlock& z, uint32_t st, uint32_t len, uint32_t lane) {
+  if (lane == 0) {
+    *z.dst_len = len;
+    *z.status = static_cast<uint8_t>(st);
+  }
+}
+
+__device__ __forceinline__ void raw_block(const ZcBlock& z, uint32_t lane) {
+  const uint32_t bh = 1u + (z.n << 3);  // (21 bits of size: n <= 128 KiB)
+  if (lane < 3) z.g[z.fh + lane] = static_cast<uint8_t>(bh >> (8u * lane));
+  for (uint32_t k = lane; k < z.n; k += 64) z.g[z.fh + 3u + k] = z.raw[k];
+  finish(z, LVKV_ZSTD_OK, z.fh + 3u + z.n, lane);
+}
+
+// ZSTD_entropyCompressSequences and the block's way into the frame, after
+// match_block: literals, sequence header, codes, tables, the backward
+// bitstream, then the compressed block or -- a body too long, or its last
+// table description too near its end -- the raw one. Both kernels' (true:
+// compressed). Sq says how a sequence is kept and which fence its home needs;
+// z where the codes and the raw block's bytes are.
+template <typename Sq>
+__device__ __forceinline__ bool block_body(const Sq& sq, const ZcBlock& z, bool no_huf, uint32_t lane,
+                                           uint64_t* stamp) {
+  uint8_t* out = z.out;
+  uint8_t* ent = z.ent;
+  const uint32_t nseq = sq.nseq;
+  const uint32_t limit = z.n - ((z.n >> 6) + 2u);  // a body at least this long: raw
+  uint32_t pos = compress_literals(out, sq.lits, sq.nlit, no_huf, ent, z.nodes, lane, stamp);
+  zcstamp(stamp, 3);
+  if (pos + 1u >= limit) return raw_block(z, lane), false;  // (the smallest body: + the count byte)
+  // sequences header
+  if (lane == 0) {
+    if (nseq < 128) {
+      out[pos] = static_cast<uint8_t>(nseq);
+    } else if (nseq < 0x7F00) {
+      out[pos] = static_cast<uint8_t>((nseq >> 8) + 0x80u);
+      out[pos + 1] = static_cast<uint8_t>(nseq);
+    } else {
+      out[pos] = 0xFF;
+      out[pos + 1] = static_cast<uint8_t>(nseq - 0x7F00u);
+      out[pos + 2] = static_cast<uint8_t>((nseq - 0x7F00u) >> 8);
+    }
+  }
+  pos += nseq < 128 ? 1u : (nseq < 0x7F00 ? 2u : 3u);
+  lds_sync();
+  if (nseq > 0) {
+    uint8_t* llc = z.llc;
+    uint8_t* ofc = llc + round16(z.smax);
+    uint8_t* mlc = ofc + round16(z.smax);
+    for (uint32_t i = lane; i < nseq; i += 64) {
+      uint32_t ll, mlb, of;
+      sq.unpack(i, &ll, &mlb, &of);
+      llc[i] = static_cast<uint8_t>(ll_code(ll));
+      ofc[i] = static_cast<uint8_t>(hibit(of));
+      mlc[i] = static_cast<uint8_t>(ml_code(mlb));
+    }
+    Sq::sync();
+    const uint32_t seq_head = pos++;
+    BitW bw;
+    bw_init(bw, out, pos);
+    FseC tll, tof, tml;
+    uint32_t at_ll, at_of, at_ml;
+    const uint32_t ty_ll = seq_table(0, llc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStLL),
+                                     bw, &tll, &at_ll, lane);
+    const uint32_t ty_of = seq_table(1, ofc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStOF),
+                                     bw, &tof, &at_of, lane);
+    const uint32_t ty_ml = seq_table(2, mlc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStML),
+                                     bw, &tml, &at_ml, lane);
+    const uint32_t last_nc = at_ml != 0xFFFFFFFFu ? at_ml : (at_of != 0xFFFFFFFFu ? at_of : at_ll);
+    zcstamp(stamp, 4);
+    if (lane == 0) out[seq_head] = static_cast<uint8_t>((ty_ll << 6) + (ty_of << 4) + (ty_ml << 2));
+    lds_sync();
+    // the backward bitstream (ZSTD_encodeSequences)
+    const uint32_t bs_start = bw_end(bw);
+    bw_init(bw, out, bs_start);
+    // the sequences 64 at a time in registers (the store's Window and the
+    // three codes of each in one more VGPR)
+    uint32_t base = (nseq - 1u) & ~63u;
+    typename Sq::Window win;
+    uint32_t rc = 0;
+    auto load = [&](uint32_t b0) {
+      const uint32_t k = b0 + lane;
+      win.load(sq, k);
+      rc = k < nseq ? (llc[k] | (static_cast<uint32_t>(ofc[k]) << 8) |
+                       (static_cast<uint32_t>(mlc[k]) << 16))
+                    : 0u;
+    };
+    uint32_t ll, mlb, of, cl, co, cm;
+    auto read = [&](uint32_t j) {
+      win.at(j, &ll, &mlb, &of);
+      const uint32_t cc = __builtin_amdgcn_readlane(rc, j);
+      cl = cc & 255u;
+      co = (cc >> 8) & 255u;
+      cm = cc >> 16;
+    };
+    load(base);
+    uint32_t i = nseq - 1u;
+    read(i - base);
+    uint32_t sm = fse_init(tml, cm), so = fse_init(tof, co), sl = fse_init(tll, cl);
+    bw_add(bw, ll, ll_bits(cl), lane);
+    bw_add(bw, mlb, ml_bits(cm), lane);
+    bw_add(bw, of, co, lane);
+    while (i > 0) {
+      --i;
+      if (i < base) {
+        base -= 64u;
+        load(base);
+      }
+      read(i - base);
+      so = fse_enc(tof, so, co, bw, lane);
+      sm = fse_enc(tml, sm, cm, bw, lane);
+      sl = fse_enc(tll, sl, cl, bw, lane);
+      bw_add(bw, ll, ll_bits(cl), lane);
+      bw_add(bw, mlb, ml_bits(cm), lane);
+      bw_add(bw, of, co, lane);
+      if (4u * bw.d >= limit) return raw_block(z, lane), false;
+    }
+    zcstamp(stamp, 5);
+    bw_add(bw, sm, tml.log, lane);
+    bw_add(bw, so, tof.log, lane);
+    bw_add(bw, sl, tll.log, lane);
+    bw_add(bw, 1u, 1, lane);
+    bw_flush(bw, lane);
+    pos = bw_end(bw);
+    // (zstd <= 1.3.4's decoder: a last table description within 4 bytes of
+    // the end makes the block raw)
+    if (last_nc != 0xFFFFFFFFu && pos - last_nc < 4u) return raw_block(z, lane), false;
+  }
+  if (pos >= limit) return raw_block(z, lane), false;
+  lds_sync();
+  const uint32_t bh = 1u + (2u << 1) + (pos << 3);
+  if (lane < 3) z.g[z.fh + lane] = static_cast<uint8_t>(bh >> (8u * lane));
+  for (uint32_t k = lane; k < pos; k += 64) z.g[z.fh + 3u + k] = out[k];
+  finish(z, LVKV_ZSTD_OK, z.fh + 3u + pos, lane);
+  return true;
 }
 
 template <typename TIdx>
@@ -1737,12 +1910,14 @@ __global__ void __launch_bounds__(64) zstd_compress_kernel(ZcArgs a) {
   const uint32_t n = a.src_len[b];
   const uint8_t* src = a.src + a.src_off[b];
   uint8_t* g = a.dst + (a.dst_off ? a.dst_off[b] : b * a.dst_stride);
-  auto finish = [&](uint32_t st, uint32_t len) {
-    if (lane == 0) {
-      a.dst_len[b] = len;
-      a.status[b] = static_cast<uint8_t>(st);
-    }
-  };
+  uint8_t* in = smem;
+  TIdx* table = reinterpret_cast<TIdx*>(smem + a.o_tbl);
+  uint32_t* tags = reinterpret_cast<uint32_t*>(smem + a.o_tag);
+  // (for the entropy stage the input region becomes the body's staging buffer,
+  // the dead table the scratch and the codes, the window slots the Huffman nodes)
+  uint8_t* ent = reinterpret_cast<uint8_t*>(table);
+  ZcBlock z{g, 0, n, src, a.dst_len + b, a.status + b, in, ent, reinterpret_cast<HNode*>(tags),
+            ent + kECodes, a.smax};
 #ifdef LVKV_PROBE_BUILD
   __shared__ uint64_t stamp_lds[16];
   uint64_t* stamp = stamp_lds;
@@ -1751,23 +1926,14 @@ __global__ void __launch_bounds__(64) zstd_compress_kernel(ZcArgs a) {
 #endif
   zcstamp(stamp, 0);
   const ZParams zp = zstd_port_params(a.level, n);
-  if (!zp.ok) return finish(LVKV_ZSTD_UNSUPPORTED, 0);
-  if (n > a.max_len) return finish(LVKV_ZSTD_TOO_LARGE, 0);
-  const uint32_t fh = frame_header(g, zp.wlog, n, lane);
+  if (!zp.ok) return finish(z, LVKV_ZSTD_UNSUPPORTED, 0, lane);
+  if (n > a.max_len) return finish(z, LVKV_ZSTD_TOO_LARGE, 0, lane);
+  z.fh = frame_header(g, zp.wlog, n, lane);
   if (n == 0) {
-    if (lane < 3) g[fh + lane] = lane == 0 ? 1 : 0;  // the last (empty) raw block
-    return finish(LVKV_ZSTD_OK, fh + 3u);
+    if (lane < 3) g[z.fh + lane] = lane == 0 ? 1 : 0;  // the last (empty) raw block
+    return finish(z, LVKV_ZSTD_OK, z.fh + 3u, lane);
   }
-  auto raw_block = [&]() {
-    const uint32_t bh = 1u + (n << 3);
-    if (lane < 3) g[fh + lane] = static_cast<uint8_t>(bh >> (8u * lane));
-    for (uint32_t k = lane; k < n; k += 64) g[fh + 3u + k] = src[k];
-    finish(LVKV_ZSTD_OK, fh + 3u + n);
-  };
-  if (n < 7) return raw_block();  // (MIN_CBLOCK_SIZE + header + 1)
-  uint8_t* in = smem;
-  TIdx* table = reinterpret_cast<TIdx*>(smem + a.o_tbl);
-  uint32_t* tags = reinterpret_cast<uint32_t*>(smem + a.o_tag);
+  if (n < 7) return raw_block(z, lane);  // (MIN_CBLOCK_SIZE + header + 1)
   Seqs sq;
   // the literals go to the block's own frame slot in HBM while the table is
   // in use (room: ZSTD_compressBound(n) - n >= kLitStage + 22 for n <=
@@ -1778,7 +1944,7 @@ __global__ void __launch_bounds__(64) zstd_compress_kernel(ZcArgs a) {
   sq.sof = reinterpret_cast<uint16_t*>(smem + a.o_sof);
   sq.nlit = 0;
   sq.nseq = 0;
-  stage(in, src, n, 16, lane);
+  stage(in, src, n, lane);
   {
     const uint32_t tw = ((sizeof(TIdx) << zp.hlog) + 3u) >> 2;
     uint32_t* tz = reinterpret_cast<uint32_t*>(table);
@@ -1796,123 +1962,7 @@ __global__ void __launch_bounds__(64) zstd_compress_kernel(ZcArgs a) {
     lds_sync();
   }
   zcstamp(stamp, 2);
-  // ---- entropy (the input region becomes the block's staging buffer)
-  uint8_t* out = in;
-  uint8_t* ent = reinterpret_cast<uint8_t*>(table);
-  HNode* nodes = reinterpret_cast<HNode*>(tags);
-  const uint32_t nseq = sq.nseq;
-  const uint32_t limit = n - ((n >> 6) + 2u);  // a body at least this long: raw
-  uint32_t pos = compress_literals(out, sq.lits, sq.nlit, zp.tl > 0, ent, nodes, lane, stamp);
-  zcstamp(stamp, 3);
-  if (pos + 1u >= limit) return raw_block();  // (the smallest body: + the count byte)
-  // sequences header
-  if (lane == 0) {
-    if (nseq < 128) {
-      out[pos] = static_cast<uint8_t>(nseq);
-    } else if (nseq < 0x7F00) {
-      out[pos] = static_cast<uint8_t>((nseq >> 8) + 0x80u);
-      out[pos + 1] = static_cast<uint8_t>(nseq);
-    } else {
-      out[pos] = 0xFF;
-      out[pos + 1] = static_cast<uint8_t>(nseq - 0x7F00u);
-      out[pos + 2] = static_cast<uint8_t>((nseq - 0x7F00u) >> 8);
-    }
-  }
-  pos += nseq < 128 ? 1u : (nseq < 0x7F00 ? 2u : 3u);
-  lds_sync();
-  if (nseq > 0) {
-    uint8_t* llc = ent + kECodes;
-    uint8_t* ofc = llc + round16(a.smax);
-    uint8_t* mlc = ofc + round16(a.smax);
-    for (uint32_t i = lane; i < nseq; i += 64) {
-      const uint32_t v = sq.sll[i];
-      const uint32_t ll = v & 0xFFFFu, mlb = v >> 16;
-      llc[i] = static_cast<uint8_t>(ll_code(ll));
-      ofc[i] = static_cast<uint8_t>(hibit(sq.sof[i]));
-      mlc[i] = static_cast<uint8_t>(ml_code(mlb));
-    }
-    lds_sync();
-    const uint32_t seq_head = pos++;
-    BitW bw;
-    bw_init(bw, out, pos);
-    FseC tll, tof, tml;
-    uint32_t at_ll, at_of, at_ml;
-    const uint32_t ty_ll = seq_table(0, llc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStLL),
-                                     bw, &tll, &at_ll, lane);
-    const uint32_t ty_of = seq_table(1, ofc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStOF),
-                                     bw, &tof, &at_of, lane);
-    const uint32_t ty_ml = seq_table(2, mlc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStML),
-                                     bw, &tml, &at_ml, lane);
-    uint32_t last_nc = at_ml != 0xFFFFFFFFu ? at_ml : (at_of != 0xFFFFFFFFu ? at_of : at_ll);
-    zcstamp(stamp, 4);
-    if (lane == 0) out[seq_head] = static_cast<uint8_t>((ty_ll << 6) + (ty_of << 4) + (ty_ml << 2));
-    lds_sync();
-    // the backward bitstream (ZSTD_encodeSequences)
-    const uint32_t bs_start = bw_end(bw);
-    bw_init(bw, out, bs_start);
-    // the sequences 64 at a time in registers (lane k: sequence base + k),
-    // read by the serial coder with v_readlane
-    uint32_t base = (nseq - 1u) & ~63u;
-    uint32_t rv = 0, ro = 0, rc = 0;
-    auto load = [&](uint32_t b0) {
-      const uint32_t k = b0 + lane;
-      rv = k < nseq ? sq.sll[k] : 0u;
-      ro = k < nseq ? sq.sof[k] : 0u;
-      rc = k < nseq ? (llc[k] | (static_cast<uint32_t>(ofc[k]) << 8) |
-                       (static_cast<uint32_t>(mlc[k]) << 16))
-                    : 0u;
-    };
-    load(base);
-    uint32_t i = nseq - 1u;
-    uint32_t v = __builtin_amdgcn_readlane(rv, i - base), of = __builtin_amdgcn_readlane(ro, i - base);
-    uint32_t cc = __builtin_amdgcn_readlane(rc, i - base);
-    uint32_t cl = cc & 255u, co = (cc >> 8) & 255u, cm = cc >> 16;
-    uint32_t sm = fse_init(tml, cm), so = fse_init(tof, co), sl = fse_init(tll, cl);
-    bw_add(bw, v & 0xFFFFu, ll_bits(cl), lane);
-    bw_add(bw, v >> 16, ml_bits(cm), lane);
-    bw_add(bw, of, co, lane);
-    bool over = false;
-    while (i > 0) {
-      --i;
-      if (i < base) {
-        base -= 64u;
-        load(base);
-      }
-      v = __builtin_amdgcn_readlane(rv, i - base);
-      of = __builtin_amdgcn_readlane(ro, i - base);
-      cc = __builtin_amdgcn_readlane(rc, i - base);
-      cl = cc & 255u;
-      co = (cc >> 8) & 255u;
-      cm = cc >> 16;
-      so = fse_enc(tof, so, co, bw, lane);
-      sm = fse_enc(tml, sm, cm, bw, lane);
-      sl = fse_enc(tll, sl, cl, bw, lane);
-      bw_add(bw, v & 0xFFFFu, ll_bits(cl), lane);
-      bw_add(bw, v >> 16, ml_bits(cm), lane);
-      bw_add(bw, of, co, lane);
-      if (4u * bw.d >= limit) {
-        over = true;
-        break;
-      }
-    }
-    if (over) return raw_block();
-    zcstamp(stamp, 5);
-    bw_add(bw, sm, tml.log, lane);
-    bw_add(bw, so, tof.log, lane);
-    bw_add(bw, sl, tll.log, lane);
-    bw_add(bw, 1u, 1, lane);
-    bw_flush(bw, lane);
-    pos = bw_end(bw);
-    // (zstd <= 1.3.4's decoder: a last table description within 4 bytes of
-    // the end makes the block raw)
-    if (last_nc != 0xFFFFFFFFu && pos - last_nc < 4u) return raw_block();
-  }
-  if (pos >= limit) return raw_block();
-  lds_sync();
-  const uint32_t bh = 1u + (2u << 1) + (pos << 3);
-  if (lane < 3) g[fh + lane] = static_cast<uint8_t>(bh >> (8u * lane));
-  for (uint32_t k = lane; k < pos; k += 64) g[fh + 3u + k] = out[k];
-  finish(LVKV_ZSTD_OK, fh + 3u + pos);
+  if (!block_body(sq, z, zp.tl > 0, lane, stamp)) return;
   zcstamp(stamp, 6);
 #ifdef LVKV_PROBE_BUILD
   lds_sync();
@@ -1923,7 +1973,7 @@ __global__ void __launch_bounds__(64) zstd_compress_kernel(ZcArgs a) {
 // ---- blocks past the LDS plan: 20,481 - 131,072 bytes -------
 //
 // One Zstd block a frame still (ZSTD_BLOCKSIZE_MAX = 128 KiB), the same
-// match finder and entropy coders, another home for the data: the hash table
+// match_block and block_body, another home for the data: the hash table
 // (u32 entries, up to 2^15 of them) and the window slots stay in LDS; the
 // block -- a padded copy, so that the 4- and 8-byte reads behave as on the
 // LDS copy and no frame byte depends on what follows the block in the
@@ -1957,182 +2007,31 @@ struct ZcBigArgs {
   uint32_t level_ok;                    // the level is a ZSTD_fast one at these sizes
 };
 
-// Everything this wave wrote to HBM is visible to its later reads (other
-// lanes' included): the HBM-side counterpart of lds_sync().
-__device__ __forceinline__ void hbm_sync() {
-  __threadfence();
-  lds_sync();
-}
-
-// The block's copy: dst[0, n) = src[0, n), then 16 zero bytes (up to the
-// dword). dst is dword-aligned; src is read in aligned dwords that hold at
-// least one byte of the block.
-__device__ __forceinline__ void stage_big(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
-  const uint32_t mis = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(src)) & 3u;
-  const uint32_t* s = reinterpret_cast<const uint32_t*>(src - mis);
-  const uint32_t nd = (n + 3u) >> 2, ndp = (n + 16u + 3u) >> 2;
-  for (uint32_t i = lane; i < ndp; i += 64) {
-    uint32_t v = 0;
-    if (i < nd) {
-      const uint32_t lo = s[i];
-      const uint32_t hi = (mis != 0 && 4u * (i + 1u) < mis + n) ? s[i + 1] : 0u;
-      v = __builtin_amdgcn_alignbyte(hi, lo, mis);
-      const uint32_t rem = n - 4u * i;
-      if (rem < 4u) v &= (1u << (8u * rem)) - 1u;
-    }
-    reinterpret_cast<uint32_t*>(dst)[i] = v;
-  }
-}
-
 __device__ __forceinline__ void zc_big_block(const ZcBigArgs& a, uint32_t b, uint32_t n, uint8_t* slot,
                                              uint8_t* smem, uint32_t lane, uint64_t* stamp) {
   const uint8_t* src = a.src + a.src_off[b];
   uint8_t* g = a.dst + (a.dst_off ? a.dst_off[b] : b * a.dst_stride);
-  auto finish = [&](uint32_t st, uint32_t len) {
-    if (lane == 0) {
-      a.dst_len[b] = len;
-      a.status[b] = static_cast<uint8_t>(st);
-    }
-  };
-  const ZParams zp = zstd_port_params(a.level, n);
-  if (!zp.ok) return finish(LVKV_ZSTD_UNSUPPORTED, 0);
-  const uint32_t fh = frame_header(g, zp.wlog, n, lane);
   const uint8_t* in = slot;
-  auto raw_block = [&]() {
-    const uint32_t bh = 1u + (n << 3);  // (21 bits of size: n <= 128 KiB)
-    if (lane < 3) g[fh + lane] = static_cast<uint8_t>(bh >> (8u * lane));
-    for (uint32_t k = lane; k < n; k += 64) g[fh + 3u + k] = in[k];
-    finish(LVKV_ZSTD_OK, fh + 3u + n);
-  };
   uint32_t* table = reinterpret_cast<uint32_t*>(smem);
   uint32_t* tags = reinterpret_cast<uint32_t*>(smem + a.o_tag);
+  // (the body in LDS over the dead table, the codes in the slot)
+  ZcBlock z{g, 0, n, in, a.dst_len + b, a.status + b, smem, smem + a.o_ent,
+            reinterpret_cast<HNode*>(tags), slot + a.s_code, a.smax};
+  const ZParams zp = zstd_port_params(a.level, n);
+  if (!zp.ok) return finish(z, LVKV_ZSTD_UNSUPPORTED, 0, lane);
+  z.fh = frame_header(g, zp.wlog, n, lane);
   SeqsBig sq;
   sq.lits = slot + a.s_lit;
   sq.sq = reinterpret_cast<uint32_t*>(slot + a.s_seq);
   sq.nlit = 0;
   sq.nseq = 0;
-  stage_big(slot, src, n, lane);
+  stage(slot, src, n, lane);
   for (uint32_t k = lane; k < (1u << zp.hlog); k += 64) table[k] = 0;
   for (uint32_t k = lane; k < kTags; k += 64) tags[k] = 0xFFFFFFFFu;
   hbm_sync();
   match_block<uint32_t, SeqsBig>(in, n, table, tags, zp, sq, lane);
   hbm_sync();
-  // ---- entropy: the body in LDS over the dead table
-  uint8_t* out = smem;
-  uint8_t* ent = smem + a.o_ent;
-  HNode* nodes = reinterpret_cast<HNode*>(tags);
-  const uint32_t nseq = sq.nseq;
-  const uint32_t limit = n - ((n >> 6) + 2u);
-  uint32_t pos = compress_literals(out, sq.lits, sq.nlit, zp.tl > 0, ent, nodes, lane, stamp);
-  if (pos + 1u >= limit) return raw_block();
-  if (lane == 0) {
-    if (nseq < 128) {
-      out[pos] = static_cast<uint8_t>(nseq);
-    } else if (nseq < 0x7F00) {
-      out[pos] = static_cast<uint8_t>((nseq >> 8) + 0x80u);
-      out[pos + 1] = static_cast<uint8_t>(nseq);
-    } else {
-      out[pos] = 0xFF;
-      out[pos + 1] = static_cast<uint8_t>(nseq - 0x7F00u);
-      out[pos + 2] = static_cast<uint8_t>((nseq - 0x7F00u) >> 8);
-    }
-  }
-  pos += nseq < 128 ? 1u : (nseq < 0x7F00 ? 2u : 3u);
-  lds_sync();
-  if (nseq > 0) {
-    uint8_t* llc = slot + a.s_code;
-    uint8_t* ofc = llc + round16(a.smax);
-    uint8_t* mlc = ofc + round16(a.smax);
-    auto unpack = [&](uint32_t k, uint32_t* ll, uint32_t* mlb, uint32_t* of) {
-      const uint32_t w0 = sq.sq[2u * k], w1 = sq.sq[2u * k + 1u];
-      *ll = w0 & 0x1FFFFu;
-      *mlb = (w0 >> 17) | ((w1 >> 18) << 15);
-      *of = w1 & 0x3FFFFu;
-    };
-    for (uint32_t i = lane; i < nseq; i += 64) {
-      uint32_t ll, mlb, of;
-      unpack(i, &ll, &mlb, &of);
-      llc[i] = static_cast<uint8_t>(ll_code(ll));
-      ofc[i] = static_cast<uint8_t>(hibit(of));
-      mlc[i] = static_cast<uint8_t>(ml_code(mlb));
-    }
-    hbm_sync();
-    const uint32_t seq_head = pos++;
-    BitW bw;
-    bw_init(bw, out, pos);
-    FseC tll, tof, tml;
-    uint32_t at_ll, at_of, at_ml;
-    const uint32_t ty_ll = seq_table(0, llc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStLL),
-                                     bw, &tll, &at_ll, lane);
-    const uint32_t ty_of = seq_table(1, ofc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStOF),
-                                     bw, &tof, &at_of, lane);
-    const uint32_t ty_ml = seq_table(2, mlc, nseq, ent, reinterpret_cast<uint16_t*>(ent + kEStML),
-                                     bw, &tml, &at_ml, lane);
-    const uint32_t last_nc = at_ml != 0xFFFFFFFFu ? at_ml : (at_of != 0xFFFFFFFFu ? at_of : at_ll);
-    if (lane == 0) out[seq_head] = static_cast<uint8_t>((ty_ll << 6) + (ty_of << 4) + (ty_ml << 2));
-    lds_sync();
-    const uint32_t bs_start = bw_end(bw);
-    bw_init(bw, out, bs_start);
-    // 64 sequences at a time in registers, as the first kernel
-    uint32_t base = (nseq - 1u) & ~63u;
-    uint32_t rl = 0, rm = 0, ro = 0, rc = 0;
-    auto load = [&](uint32_t b0) {
-      const uint32_t k = b0 + lane;
-      rl = rm = ro = rc = 0;
-      if (k < nseq) {
-        unpack(k, &rl, &rm, &ro);
-        rc = llc[k] | (static_cast<uint32_t>(ofc[k]) << 8) | (static_cast<uint32_t>(mlc[k]) << 16);
-      }
-    };
-    load(base);
-    uint32_t i = nseq - 1u;
-    uint32_t ll = __builtin_amdgcn_readlane(rl, i - base), mlb = __builtin_amdgcn_readlane(rm, i - base);
-    uint32_t of = __builtin_amdgcn_readlane(ro, i - base), cc = __builtin_amdgcn_readlane(rc, i - base);
-    uint32_t cl = cc & 255u, co = (cc >> 8) & 255u, cm = cc >> 16;
-    uint32_t sm = fse_init(tml, cm), so = fse_init(tof, co), sl = fse_init(tll, cl);
-    bw_add(bw, ll, ll_bits(cl), lane);
-    bw_add(bw, mlb, ml_bits(cm), lane);
-    bw_add(bw, of, co, lane);
-    bool over = false;
-    while (i > 0) {
-      --i;
-      if (i < base) {
-        base -= 64u;
-        load(base);
-      }
-      ll = __builtin_amdgcn_readlane(rl, i - base);
-      mlb = __builtin_amdgcn_readlane(rm, i - base);
-      of = __builtin_amdgcn_readlane(ro, i - base);
-      cc = __builtin_amdgcn_readlane(rc, i - base);
-      cl = cc & 255u;
-      co = (cc >> 8) & 255u;
-      cm = cc >> 16;
-      so = fse_enc(tof, so, co, bw, lane);
-      sm = fse_enc(tml, sm, cm, bw, lane);
-      sl = fse_enc(tll, sl, cl, bw, lane);
-      bw_add(bw, ll, ll_bits(cl), lane);
-      bw_add(bw, mlb, ml_bits(cm), lane);
-      bw_add(bw, of, co, lane);
-      if (4u * bw.d >= limit) {
-        over = true;
-        break;
-      }
-    }
-    if (over) return raw_block();
-    bw_add(bw, sm, tml.log, lane);
-    bw_add(bw, so, tof.log, lane);
-    bw_add(bw, sl, tll.log, lane);
-    bw_add(bw, 1u, 1, lane);
-    bw_flush(bw, lane);
-    pos = bw_end(bw);
-    if (last_nc != 0xFFFFFFFFu && pos - last_nc < 4u) return raw_block();
-  }
-  if (pos >= limit) return raw_block();
-  lds_sync();
-  const uint32_t bh = 1u + (2u << 1) + (pos << 3);
-  if (lane < 3) g[fh + lane] = static_cast<uint8_t>(bh >> (8u * lane));
-  for (uint32_t k = lane; k < pos; k += 64) g[fh + 3u + k] = out[k];
-  finish(LVKV_ZSTD_OK, fh + 3u + pos);
+  block_body(sq, z, zp.tl > 0, lane, stamp);
 }
 
 __global__ void __launch_bounds__(64) zstd_compress_big_kernel(ZcBigArgs a) {
@@ -2140,7 +2039,7 @@ __global__ void __launch_bounds__(64) zstd_compress_big_kernel(ZcBigArgs a) {
   const uint32_t lane = threadIdx.x;
   uint8_t* slot = a.slots + blockIdx.x * a.slot_bytes;
 #ifdef LVKV_PROBE_BUILD
-  __shared__ uint64_t stamp_lds[16];  // (compress_literals' phase stamps: not reported)
+  __shared__ uint64_t stamp_lds[16];  // (block_body's phase stamps: not reported)
   uint64_t* stamp = stamp_lds;
 #else
   uint64_t* stamp = nullptr;

@@ -114,6 +114,22 @@ def test_emulated_workgroup_takes_many_blocks(emu, level):
         (r.stdout + r.stderr)[-3000:]
 
 
+def test_emulated_first_kernel_on_the_fixtures(emu):
+    """The first kernel alone over every committed input it takes (at most
+    20,480 bytes; tests/test_zstd_write.py::test_fixtures_reach_the_rare_paths
+    says which paths they reach), at level 1: block_body is the body both
+    kernels run, and most of its paths are reached by small blocks only."""
+    spec = json.loads((GOLDEN / "zstd_write.json").read_text())
+    nb = sum(1 for n in spec["inputs"] if n <= 20480)
+    assert nb > 0
+    r = subprocess.run([sys.executable, str(REPO / "tools/simt_emu/zstdc_check.py"), "fixtures",
+                        "1"], capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert f"{nb} blocks, 0 differ from the oracle" in r.stdout, r.stdout
+    assert "Sanitizer" not in r.stdout + r.stderr and "runtime error" not in r.stdout + r.stderr, \
+        (r.stdout + r.stderr)[-3000:]
+
+
 # ---- GPU -----------------------------------------------------------------------
 
 def _pack(torch, dev, blobs, skew=0):
