@@ -256,6 +256,76 @@ int lvkv_sst_write_table_device(const void* d_raw, const uint64_t* d_raw_off,
                                 uint64_t* d_handle_off, uint32_t* d_handle_size, uint8_t* d_type,
                                 uint8_t* d_status, lvkv_sst_table_report* d_report, void* stream);
 
+/* ---- the data blocks: TableBuilder::Add on the device ----------------------- */
+
+#define LVKV_BUILD_OK 0
+#define LVKV_BUILD_UNSORTED 1     /* entry first_bad_entry is not greater than the one before it */
+#define LVKV_BUILD_BAD_KEY 2      /* key_format 1 and a key under 8 bytes */
+#define LVKV_BUILD_CAPACITY 3     /* more blocks than max_blocks, or more bytes than raw_capacity */
+#define LVKV_BUILD_TOO_LARGE 4    /* a block's contents would pass 2^31 - 1 bytes */
+
+typedef struct lvkv_sst_build_report {
+  int32_t  status;
+  uint32_t first_bad_entry;   /* lowest offending entry for UNSORTED / BAD_KEY, else 0xFFFFFFFF */
+  uint32_t nblocks;           /* blocks cut; with CAPACITY: the number that would be needed */
+  uint32_t max_block_len;     /* longest block's contents (max_len for the writer) */
+  uint32_t max_key_len;       /* longest key (max_key_len for the table writer) */
+  uint64_t num_entries;
+  uint64_t raw_bytes;         /* end of the last block in d_raw; with CAPACITY: the bytes needed */
+} lvkv_sst_build_report;
+
+/* The scratch of lvkv_sst_build_blocks_device, and an upper bound of what it
+ * writes to d_raw whatever the entries are (5-byte varints, a restart per
+ * entry, a block per entry with 15 bytes of padding). Both never decrease
+ * when an argument grows. */
+size_t   lvkv_sst_build_blocks_scratch_bytes(size_t nentries, uint32_t restart_interval);
+uint64_t lvkv_sst_build_blocks_raw_bound(size_t nentries, uint64_t total_key_bytes,
+                                         uint64_t total_value_bytes, uint32_t restart_interval);
+
+/*
+ * TableBuilder::Add over sorted entries, then the Flush() that Finish() begins
+ * with (table/table_builder.cc:94-123, 213-215), in one stream-ordered call:
+ * entry i has key d_keys[d_key_off[i], + d_key_len[i]) and value
+ * d_vals[d_val_off[i], + d_val_len[i]) (the two buffers may be one). Out come
+ * the data blocks BlockBuilder::Add + Finish build (table/block_builder.cc:
+ * shared is the byte-wise common prefix with the previous key of the same
+ * block, 0 at entries whose index in the block is a multiple of
+ * restart_interval), cut after the entry with which the block's
+ * CurrentSizeEstimate() reaches block_size (>=; block_size 0: an entry a
+ * block). Block b's contents are d_raw[d_raw_off[b], + d_raw_len[b]);
+ * d_raw_off[0] = 0 and d_raw_off[b] = the end of block b - 1 rounded up to 16
+ * (the bytes between blocks are not written): the first three arguments of
+ * lvkv_sst_write_table_device.
+ *
+ * Order: key_format 0, each key byte-wise greater than the one before it; 1,
+ * greater under InternalKeyComparator (db/dbformat.cc:47-63: user key
+ * ascending, then the trailing 8 bytes as a little-endian u64 descending),
+ * and every key 8 bytes or longer.
+ *
+ * No synchronisation, no copy to the host: d_report (device memory) says how
+ * it went. On a status other than OK nothing at all is written to d_raw,
+ * d_raw_off or d_raw_len (the layout is known before the first byte is
+ * copied), and never anything at or past d_raw + raw_capacity, d_raw_off +
+ * max_blocks or d_raw_len + max_blocks. BAD_KEY is reported before UNSORTED,
+ * those before TOO_LARGE, that before CAPACITY; first_bad_entry is the lowest
+ * entry of the reported kind. With BAD_KEY and UNSORTED nblocks,
+ * max_block_len and raw_bytes are 0; with CAPACITY they are what the call
+ * needs, so that it can be repeated; max_key_len and num_entries always hold.
+ *
+ * nentries == 0, before every other check: LVKV_OK, and a report of no blocks
+ * where d_report is not null (every pointer may be null). LVKV_ERR_INVALID,
+ * before any launch: a null pointer, restart_interval 0, key_format outside
+ * 0..1, nentries >= 2^31, scratch_bytes under the sizing function's value.
+ */
+int lvkv_sst_build_blocks_device(
+    const void* d_keys, const uint64_t* d_key_off, const uint32_t* d_key_len,
+    const void* d_vals, const uint64_t* d_val_off, const uint32_t* d_val_len,
+    size_t nentries, uint32_t block_size, uint32_t restart_interval, int key_format,
+    void* d_scratch, size_t scratch_bytes,
+    void* d_raw, uint64_t raw_capacity,
+    uint64_t* d_raw_off, uint32_t* d_raw_len, size_t max_blocks,
+    lvkv_sst_build_report* d_report, void* stream);
+
 /* ReadBlock verdicts */
 #define LVKV_READ_OK 0
 #define LVKV_READ_CHECKSUM 1        /* "block checksum mismatch" (table/format.cc:95-98) */

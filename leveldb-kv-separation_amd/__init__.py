@@ -180,6 +180,13 @@ def _load() -> ctypes.CDLL:
     L.lvkv_sst_write_table_device.argtypes = [vp, vp, vp, sz, i32, i32, u32, i32, i32, u32, vp, sz,
                                               vp, u64, vp, vp, vp, vp, vp, vp]
     L.lvkv_sst_write_table_device.restype = i32
+    L.lvkv_sst_build_blocks_scratch_bytes.argtypes = [sz, u32]
+    L.lvkv_sst_build_blocks_scratch_bytes.restype = sz
+    L.lvkv_sst_build_blocks_raw_bound.argtypes = [sz, u64, u64, u32]
+    L.lvkv_sst_build_blocks_raw_bound.restype = u64
+    L.lvkv_sst_build_blocks_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, u32, u32, i32, vp, sz,
+                                               vp, u64, vp, vp, sz, vp, vp]
+    L.lvkv_sst_build_blocks_device.restype = i32
     L.lvkv_sst_read_blocks_device.argtypes = [vp, vp, vp, sz, i32, vp, vp, vp, vp, vp, u32, vp]
     L.lvkv_sst_read_blocks_device.restype = i32
     L.lvkv_strerror.argtypes = [i32]
@@ -906,6 +913,96 @@ def sst_write_table(raw, offsets, lengths, *, compression: int = 1, zstd_level: 
         stream.synchronize()
     report = SstTableReport.from_buffer_copy(bytes(rep.cpu().numpy())).as_dict()
     return file, hoff, hsize, typ, status, report
+
+
+BUILD_OK, BUILD_UNSORTED, BUILD_BAD_KEY, BUILD_CAPACITY, BUILD_TOO_LARGE = range(5)
+
+
+class SstBuildReport(ctypes.Structure):
+    """lvkv_sst_build_report (include/lvkv_snappy.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("first_bad_entry", ctypes.c_uint32),
+                ("nblocks", ctypes.c_uint32), ("max_block_len", ctypes.c_uint32),
+                ("max_key_len", ctypes.c_uint32), ("num_entries", ctypes.c_uint64),
+                ("raw_bytes", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def sst_build_blocks(keys, key_off, key_len, vals, val_off, val_len, *, block_size: int = 4096,
+                     restart_interval: int = 16, key_format: int = 1, raw=None,
+                     max_blocks: Optional[int] = None, scratch=None, stream=None):
+    """TableBuilder::Add over sorted entries (lvkv_sst_build_blocks_device):
+    entry i is keys[key_off[i] : key_off[i] + key_len[i]] -> vals[val_off[i] :
+    val_off[i] + val_len[i]], in comparator order (key_format 1: internal
+    keys, 0: plain byte strings). The data blocks BlockBuilder builds, cut as
+    TableBuilder cuts them at block_size, land in `raw` (allocated by
+    lvkv_sst_build_blocks_raw_bound when None; all of it may be written) at
+    raw_off[b], raw_len[b] for b < report['nblocks'] (arrays of max_blocks,
+    default: an entry a block). Returns (raw, raw_off int64, raw_len int32,
+    report dict); report['status'] is BUILD_*, and nothing is written unless
+    it is BUILD_OK. The report is the one thing read back."""
+    torch = _torch()
+    n = key_off.numel()
+    dev = keys.device
+    if not (key_len.numel() == val_off.numel() == val_len.numel() == n):
+        raise ValueError("the entry arrays differ in length")
+    if max_blocks is None:
+        max_blocks = n
+    if raw is None:
+        kb = int(key_len.to(torch.int64).sum().item()) if n else 0
+        vb = int(val_len.to(torch.int64).sum().item()) if n else 0
+        raw = torch.empty(max(1, int(_lib.lvkv_sst_build_blocks_raw_bound(
+            n, kb, vb, restart_interval))), dtype=torch.uint8, device=dev)
+    if scratch is None:
+        scratch = torch.empty(int(_lib.lvkv_sst_build_blocks_scratch_bytes(n, restart_interval)),
+                              dtype=torch.uint8, device=dev)
+    raw_off = torch.empty(max(1, max_blocks), dtype=torch.int64, device=dev)[:max_blocks]
+    raw_len = torch.empty(max(1, max_blocks), dtype=torch.int32, device=dev)[:max_blocks]
+    rep = torch.zeros(ctypes.sizeof(SstBuildReport), dtype=torch.uint8, device=dev)
+    b8 = (torch.uint8, torch.int8)
+    with torch.cuda.device(dev):
+        rc = _lib.lvkv_sst_build_blocks_device(
+            _dev_ptr(keys, "keys", b8) if n else None,
+            _dev_ptr(key_off, "key_off", (torch.int64,)) if n else None,
+            _dev_ptr(key_len, "key_len", (torch.int32,)) if n else None,
+            _dev_ptr(vals, "vals", b8) if n else None,
+            _dev_ptr(val_off, "val_off", (torch.int64,)) if n else None,
+            _dev_ptr(val_len, "val_len", (torch.int32,)) if n else None,
+            n, int(block_size), int(restart_interval), int(key_format),
+            _dev_ptr(scratch, "scratch", b8), scratch.numel(), _dev_ptr(raw, "raw", b8),
+            raw.numel(), _dev_ptr(raw_off, "raw_off", (torch.int64,)),
+            _dev_ptr(raw_len, "raw_len", (torch.int32,)), int(max_blocks),
+            _dev_ptr(rep, "report"), _stream_handle(stream, dev))
+    _check("lvkv_sst_build_blocks_device", rc)
+    if stream is not None:
+        stream.synchronize()
+    report = SstBuildReport.from_buffer_copy(bytes(rep.cpu().numpy())).as_dict()
+    return raw, raw_off, raw_len, report
+
+
+def sst_build_table(keys, key_off, key_len, vals, val_off, val_len, *, block_size: int = 4096,
+                    restart_interval: int = 16, key_format: int = 1, compression: int = 1,
+                    zstd_level: int = 1, filter_bits_per_key: int = 10, file=None,
+                    file_capacity: Optional[int] = None, stream=None):
+    """Sorted entries -> the whole table image: sst_build_blocks, then
+    sst_write_table on the blocks it cut, with max_len and max_key_len from
+    the build's report. Returns sst_write_table's tuple and the build report:
+    (file, handle offsets, handle sizes, types, status, table report, build
+    report). When the build's status is not BUILD_OK no table is written and
+    the first six are None."""
+    raw, raw_off, raw_len, build = sst_build_blocks(
+        keys, key_off, key_len, vals, val_off, val_len, block_size=block_size,
+        restart_interval=restart_interval, key_format=key_format, stream=stream)
+    if build["status"] != BUILD_OK:
+        return (None,) * 6 + (build,)
+    nb = build["nblocks"]
+    out = sst_write_table(raw, raw_off[:nb], raw_len[:nb], compression=compression,
+                          zstd_level=zstd_level, max_len=build["max_block_len"],
+                          key_format=key_format, filter_bits_per_key=filter_bits_per_key,
+                          max_key_len=build["max_key_len"], file=file,
+                          file_capacity=file_capacity, stream=stream)
+    return out + (build,)
 
 
 def sst_read_blocks(file, handle_off, handle_size, *, max_ulen: int, verify: bool = True,

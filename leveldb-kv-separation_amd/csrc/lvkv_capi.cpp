@@ -1053,6 +1053,66 @@ int lvkv_sst_write_table_device(const void* d_raw, const uint64_t* d_raw_off,
                                &ctl->tail_count, hs);
 }
 
+size_t lvkv_sst_build_blocks_scratch_bytes(size_t nentries, uint32_t restart_interval) {
+  (void)restart_interval;  // (the arrays are per entry whatever the interval)
+  return 256u + static_cast<size_t>(sst_build_plan(nentries).bytes);  // alignment slack
+}
+
+uint64_t lvkv_sst_build_blocks_raw_bound(size_t nentries, uint64_t total_key_bytes,
+                                         uint64_t total_value_bytes, uint32_t restart_interval) {
+  (void)restart_interval;  // (a block an entry: every entry a restart point)
+  // three 5-byte varints, a restart, a block's count and its padding
+  return total_key_bytes + total_value_bytes + uint64_t{nentries} * (15u + 4u + 4u + 15u);
+}
+
+int lvkv_sst_build_blocks_device(const void* d_keys, const uint64_t* d_key_off,
+                                 const uint32_t* d_key_len, const void* d_vals,
+                                 const uint64_t* d_val_off, const uint32_t* d_val_len,
+                                 size_t nentries, uint32_t block_size, uint32_t restart_interval,
+                                 int key_format, void* d_scratch, size_t scratch_bytes,
+                                 void* d_raw, uint64_t raw_capacity, uint64_t* d_raw_off,
+                                 uint32_t* d_raw_len, size_t max_blocks,
+                                 lvkv_sst_build_report* d_report, void* stream) {
+  SstBuildArgs a{};
+  a.report = d_report;
+  if (nentries == 0) {
+    if (!d_report) return LVKV_OK;
+    int rc = LVKV_OK;
+    if (current_ctx(&rc) == nullptr) return rc;
+    const hipError_t e = launch_sst_build(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? LVKV_OK : hip_fail(e);
+  }
+  if (!d_keys || !d_key_off || !d_key_len || !d_vals || !d_val_off || !d_val_len || !d_scratch ||
+      !d_raw || !d_raw_off || !d_raw_len || !d_report)
+    return LVKV_ERR_INVALID;
+  if (restart_interval == 0 || key_format < 0 || key_format > 1 ||
+      nentries >= (uint64_t{1} << 31) ||
+      scratch_bytes < lvkv_sst_build_blocks_scratch_bytes(nentries, restart_interval))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  a.keys = static_cast<const uint8_t*>(d_keys);
+  a.key_off = d_key_off;
+  a.key_len = d_key_len;
+  a.vals = static_cast<const uint8_t*>(d_vals);
+  a.val_off = d_val_off;
+  a.val_len = d_val_len;
+  a.n = static_cast<uint32_t>(nentries);
+  a.block_size = block_size;
+  a.restart_interval = restart_interval;
+  a.key_format = static_cast<uint32_t>(key_format);
+  a.base = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(d_scratch) + 255u) &
+                                      ~uintptr_t{255});
+  a.plan = sst_build_plan(nentries);
+  a.raw = static_cast<uint8_t*>(d_raw);
+  a.raw_capacity = raw_capacity;
+  a.raw_off = d_raw_off;
+  a.raw_len = d_raw_len;
+  a.max_blocks = max_blocks;
+  const hipError_t e = launch_sst_build(a, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
 int lvkv_sst_write_blocks_device(const void* d_raw, const uint64_t* d_raw_off,
                                  const uint32_t* d_raw_len, size_t nblocks, int compression,
                                  uint32_t max_len, void* d_scratch, void* d_file,

@@ -236,6 +236,40 @@ struct SstFinishArgs {
 // data_end, metaindex and index contents); 2: footer and report, after it.
 hipError_t launch_sst_finish(const SstFinishArgs& a, int stage, hipStream_t stream);
 
+// ---- TableBuilder::Add on the device (lvkv_sst_build.hip) -------------------
+
+// Entries a workgroup resolves the chain of block starts for in LDS; the call
+// changes path with the entry count only here (one tile, several).
+constexpr uint32_t kBuildTile = 4096;
+// Byte offsets of the call's arrays from the 256-aligned start of its scratch
+// (the control words first).
+struct SstBuildPlan {
+  uint64_t ea, ed, ef, eb;                   // u64, one more than the entries
+  uint64_t lcp, next, exit, bstart;          // u32 an entry
+  uint64_t entry;                            // u32 a tile
+  uint64_t sums;                             // the scans' tile sums
+  uint64_t bytes;
+};
+SstBuildPlan sst_build_plan(size_t nentries);
+struct SstBuildArgs {
+  const uint8_t* keys;
+  const uint64_t* key_off;
+  const uint32_t* key_len;
+  const uint8_t* vals;
+  const uint64_t* val_off;
+  const uint32_t* val_len;
+  uint32_t n, block_size, restart_interval, key_format;
+  uint8_t* base;  // the aligned scratch
+  SstBuildPlan plan;
+  uint8_t* raw;
+  uint64_t raw_capacity;
+  uint64_t* raw_off;
+  uint32_t* raw_len;
+  uint64_t max_blocks;
+  lvkv_sst_build_report* report;
+};
+hipError_t launch_sst_build(const SstBuildArgs& a, hipStream_t stream);
+
 #ifdef LVKV_PROBE_BUILD
 // Probe builds (tools/probe/liblvkv_probe.so): timestamp buffers and knobs
 // set through lvkv_debug_*, the schedule-variant and read-bandwidth launchers.
