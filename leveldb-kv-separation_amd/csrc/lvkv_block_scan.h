@@ -1,5 +1,6 @@
-// The workgroup-wide exclusive scan of the table writers (lvkv_snappy.hip's
-// slot and layout kernels, lvkv_sst_finish.hip's filter and index layouts).
+// The workgroup-wide exclusive scan of the table writers, one pass and many
+// (lvkv_sst_blocks.hip's slot and layout kernels, lvkv_sst_finish.hip's
+// filter and index layouts, lvkv_sst_build.hip's device-wide scan).
 #ifndef LVKV_BLOCK_SCAN_H_
 #define LVKV_BLOCK_SCAN_H_
 
@@ -40,6 +41,25 @@ __device__ __forceinline__ uint64_t block_scan(uint64_t local, uint64_t* wsum, u
   __syncthreads();
   *total = wsum[16];
   return wsum[w] + incl - local;
+}
+
+// The exclusive scan of n items by one workgroup, 1,024 a pass and an item a
+// thread, the running total carried from pass to pass: item i, of value(i),
+// gets place(i, carry + the values of the items before it). Returns the carry
+// after the last item. The barrier block_scan asks for between two calls is
+// here, so wsum is free again on return.
+template <typename Value, typename Place>
+__device__ __forceinline__ uint64_t block_scan_carry(uint32_t n, uint64_t carry, uint64_t* wsum,
+                                                     Value value, Place place) {
+  for (uint32_t base = 0; base < n; base += 1024) {
+    const uint32_t i = base + threadIdx.x;
+    uint64_t total;
+    const uint64_t at = carry + block_scan(i < n ? uint64_t{value(i)} : 0u, wsum, &total);
+    if (i < n) place(i, at);
+    carry += total;
+    __syncthreads();
+  }
+  return carry;
 }
 
 }  // namespace lvkv

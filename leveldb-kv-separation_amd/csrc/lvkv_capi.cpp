@@ -19,6 +19,7 @@
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
 #include "lvkv_launch.h"
+#include "lvkv_scratch.h"
 #include "lvkv_snappy.h"
 #include "lvkv_tables.h"
 
@@ -793,7 +794,7 @@ int lvkv_snappy_compress_device(const void* d_src, const uint64_t* d_src_off,
   if (current_ctx(&rc) == nullptr) return rc;
   const hipError_t e = launch_snappy_compress(
       static_cast<const uint8_t*>(d_src), d_src_off, d_src_len, static_cast<uint8_t*>(d_dst),
-      d_dst_off, d_dst_len, d_status, static_cast<uint32_t>(nblocks), max_len,
+      d_dst_off, d_dst_len, d_status, static_cast<uint32_t>(nblocks), max_len, 0,
       static_cast<hipStream_t>(stream));
   return e == hipSuccess ? LVKV_OK : hip_fail(e);
 }
@@ -809,7 +810,8 @@ int lvkv_snappy_uncompressed_length_device(const void* d_src, const uint64_t* d_
   if (current_ctx(&rc) == nullptr) return rc;
   const hipError_t e = launch_snappy_uncompress(
       static_cast<const uint8_t*>(d_src), d_src_off, d_src_len, nullptr, nullptr, nullptr,
-      d_ulen, d_status, static_cast<uint32_t>(nblocks), 0, static_cast<hipStream_t>(stream));
+      d_ulen, d_status, static_cast<uint32_t>(nblocks), 0, 0, nullptr,
+      static_cast<hipStream_t>(stream));
   return e == hipSuccess ? LVKV_OK : hip_fail(e);
 }
 
@@ -826,8 +828,8 @@ int lvkv_snappy_uncompress_device(const void* d_src, const uint64_t* d_src_off,
   if (current_ctx(&rc) == nullptr) return rc;
   const hipError_t e = launch_snappy_uncompress(
       static_cast<const uint8_t*>(d_src), d_src_off, d_src_len, static_cast<uint8_t*>(d_dst),
-      d_dst_off, d_dst_cap, d_out_len, d_status, static_cast<uint32_t>(nblocks), max_ulen,
-      static_cast<hipStream_t>(stream));
+      d_dst_off, d_dst_cap, d_out_len, d_status, static_cast<uint32_t>(nblocks), max_ulen, 0,
+      nullptr, static_cast<hipStream_t>(stream));
   return e == hipSuccess ? LVKV_OK : hip_fail(e);
 }
 
@@ -929,7 +931,7 @@ size_t lvkv_sst_write_table_scratch_bytes(size_t nblocks, uint64_t total_raw_byt
                                           uint32_t max_len, uint32_t max_key_len,
                                           int filter_bits_per_key) {
   // alignment slack, the finisher's own part, the data blocks' ragged scratch
-  return 256u + sst_finish_plan(nblocks, max_key_len, filter_bits_per_key).fixed +
+  return kScratchAlign + sst_finish_plan(nblocks, max_key_len, filter_bits_per_key).fixed +
          sst_write_v2_envelope(nblocks, total_raw_bytes, max_len);
 }
 
@@ -1003,9 +1005,8 @@ int lvkv_sst_write_table_device(const void* d_raw, const uint64_t* d_raw_off,
   f.k = static_cast<uint32_t>(k);
   f.max_key_len = max_key_len;
   uint8_t* const scratch = static_cast<uint8_t*>(d_scratch);
-  f.base = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(scratch) + 255u) &
-                                      ~uintptr_t{255});
-  f.plan = sst_finish_plan(nblocks, max_key_len, filter_bits_per_key);
+  f.base = scratch_base(scratch);
+  const SstFinishPlan plan = sst_finish_plan(nblocks, max_key_len, filter_bits_per_key);
   f.file = static_cast<uint8_t*>(d_file);
   f.cap = file_capacity;
   f.hoff = d_handle_off;
@@ -1016,7 +1017,7 @@ int lvkv_sst_write_table_device(const void* d_raw, const uint64_t* d_raw_off,
   hipError_t e = launch_sst_finish(f, 0, hs);
   if (e != hipSuccess) return hip_fail(e);
   // the data blocks, from file offset 0
-  uint8_t* const data_scratch = f.base + f.plan.fixed;
+  uint8_t* const data_scratch = f.base + plan.fixed;
   const SstWriteScratch ds =
       compression == 0 || n == 0
           ? SstWriteScratch{}
@@ -1037,11 +1038,11 @@ int lvkv_sst_write_table_device(const void* d_raw, const uint64_t* d_raw_off,
   const SstWriteScratch ts =
       compression == 0
           ? SstWriteScratch{}
-          : sst_scratch_ragged(f.base + f.plan.tail_scratch, f.plan.tail_scratch_bytes, 2,
-                               compression == 2 ? f.plan.tail_max_len : 0u);
+          : sst_scratch_ragged(f.base + plan.tail_scratch, plan.tail_scratch_bytes, 2,
+                               compression == 2 ? plan.tail_max_len : 0u);
   const SstWriteDest tail_dest{&ctl->tail_base, file_capacity, &ctl->nfit_tail};
-  e = launch_sst_write_blocks(f.base + f.plan.tail_raw, ctl->t_raw_off, ctl->t_raw_len, 2,
-                              compression, f.plan.tail_max_len, ts, f.file, 0, ctl->t_hoff + 1,
+  e = launch_sst_write_blocks(f.base + plan.tail_raw, ctl->t_raw_off, ctl->t_raw_len, 2,
+                              compression, plan.tail_max_len, ts, f.file, 0, ctl->t_hoff + 1,
                               ctl->t_hsize + 1, ctl->t_type, &ctl->tail_end, zstd_level,
                               ctl->t_status, hs, &tail_dest);
   if (e != hipSuccess) return hip_fail(e);
@@ -1055,7 +1056,7 @@ int lvkv_sst_write_table_device(const void* d_raw, const uint64_t* d_raw_off,
 
 size_t lvkv_sst_build_blocks_scratch_bytes(size_t nentries, uint32_t restart_interval) {
   (void)restart_interval;  // (the arrays are per entry whatever the interval)
-  return 256u + static_cast<size_t>(sst_build_plan(nentries).bytes);  // alignment slack
+  return sst_build_scratch_bytes(nentries);
 }
 
 uint64_t lvkv_sst_build_blocks_raw_bound(size_t nentries, uint64_t total_key_bytes,
@@ -1101,9 +1102,7 @@ int lvkv_sst_build_blocks_device(const void* d_keys, const uint64_t* d_key_off,
   a.block_size = block_size;
   a.restart_interval = restart_interval;
   a.key_format = static_cast<uint32_t>(key_format);
-  a.base = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(d_scratch) + 255u) &
-                                      ~uintptr_t{255});
-  a.plan = sst_build_plan(nentries);
+  a.scratch = static_cast<uint8_t*>(d_scratch);
   a.raw = static_cast<uint8_t*>(d_raw);
   a.raw_capacity = raw_capacity;
   a.raw_off = d_raw_off;
@@ -1183,18 +1182,11 @@ int lvkv_sst_read_blocks_device(const void* d_file, const uint64_t* d_handle_off
                                 nblocks, stream);
     if (rc != LVKV_OK) return rc;
   }
-  const hipStream_t hs = static_cast<hipStream_t>(stream);
-  // raw and snappy blocks (zstd ones are left for the next launch)
-  hipError_t e = launch_sst_read_blocks(
+  const hipError_t e = launch_sst_read_blocks(
       static_cast<const uint8_t*>(d_file), d_handle_off, d_handle_size,
       static_cast<uint32_t>(nblocks), static_cast<uint8_t*>(d_out), d_out_off, d_out_cap,
-      d_out_len, d_status, verify ? d_status : nullptr, max_ulen, hs);
-  if (e != hipSuccess) return hip_fail(e);
-  // kZstdCompression blocks whose checksum held (table/format.cc:138-155)
-  e = launch_zstd_uncompress(static_cast<const uint8_t*>(d_file), d_handle_off, d_handle_size,
-                             static_cast<uint8_t*>(d_out), d_out_off, d_out_cap, d_out_len,
-                             d_status, nullptr, static_cast<uint32_t>(nblocks), max_ulen, 1,
-                             verify ? d_status : nullptr, hs);
+      d_out_len, d_status, verify ? d_status : nullptr, max_ulen,
+      static_cast<hipStream_t>(stream));
   return e == hipSuccess ? LVKV_OK : hip_fail(e);
 }
 

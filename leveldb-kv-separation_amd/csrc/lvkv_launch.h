@@ -1,7 +1,8 @@
 // Everything that crosses a translation unit inside the library, declared
 // once: the kernel launchers (each defined beside its kernels), the
-// scratch-size functions their callers size buffers with, the production
-// kernel choices, and the two codec bounds. Every file that defines one of
+// scratch-size functions their callers size buffers with (each defined beside
+// the one listing of its layout; lvkv_scratch.h has the carver), the
+// production kernel choices, and the two codec bounds. Every file that defines one of
 // these includes this header, so a signature that drifts fails to compile
 // instead of failing when the library is loaded.
 #ifndef LVKV_LAUNCH_H_
@@ -30,6 +31,9 @@ template <typename T>
 __host__ __device__ constexpr T snappy_bound(T n) {
   return 32u + n + n / 6u;
 }
+// snappy's kBlockSize: a block is compressed in fragments of this, so the
+// compressor's LDS holds any block once max_len reaches it.
+constexpr uint32_t kSnappyFragment = 1u << 16;
 static_assert(zstd_bound(0u) == 64 && zstd_bound(4096u) == 4174, "ZSTD_compressBound");
 static_assert(zstd_bound(131071u) == 131582 && zstd_bound(131072u) == 131584, "ZSTD_compressBound");
 static_assert(snappy_bound(0u) == 32 && snappy_bound(4096u) == 4810, "snappy::MaxCompressedLength");
@@ -95,15 +99,21 @@ hipError_t launch_log_gather(const uint8_t* file, const uint64_t* hdr_off, size_
                              int cus, hipStream_t stream);
 
 // ---- block codecs (lvkv_snappy.hip, lvkv_zstd.hip, lvkv_zstd_compress.hip) --
+// Compressors: dst_off == nullptr puts block b's output at b * dst_stride, and
+// a block longer than max_len is then TOO_LARGE. Decompressors: block_mode 1
+// is ReadBlock (src_off/src_len are block handles, the type byte after the
+// contents picks the codec, statuses are LVKV_READ_*), vstatus the checksum
+// verdicts (nullptr: not verified).
 
 hipError_t launch_snappy_compress(const uint8_t* src, const uint64_t* src_off,
                                   const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
                                   uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
-                                  uint32_t max_len, hipStream_t stream);
+                                  uint32_t max_len, uint64_t dst_stride, hipStream_t stream);
 hipError_t launch_snappy_uncompress(const uint8_t* src, const uint64_t* src_off,
                                     const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
                                     const uint32_t* dst_cap, uint32_t* out_len, uint8_t* status,
-                                    uint32_t nblocks, uint32_t max_ulen, hipStream_t stream);
+                                    uint32_t nblocks, uint32_t max_ulen, uint32_t block_mode,
+                                    const uint8_t* vstatus, hipStream_t stream);
 hipError_t launch_zstd_compress(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len,
                                 uint8_t* dst, const uint64_t* dst_off, uint32_t* dst_len,
                                 uint8_t* status, uint32_t nblocks, uint32_t max_len, int level,
@@ -120,12 +130,13 @@ hipError_t launch_zstd_uncompress(const uint8_t* src, const uint64_t* src_off,
                                   uint32_t* detail, uint32_t nblocks, uint32_t max_ulen,
                                   uint32_t block_mode, const uint8_t* vstatus, hipStream_t stream);
 
-// ---- the block writer and reader (lvkv_snappy.hip) --------------------------
+// ---- the block writer and reader (lvkv_sst_blocks.hip) ----------------------
 
 // What a call of the writer works on besides the caller's arrays: where each
 // block's compressed form goes and the per-block arrays of the pipeline,
 // carved out of the caller's scratch by one of the two functions below (all
-// null for compression 0 and for an empty batch).
+// null for compression 0 and for an empty batch). Each of the two layouts is
+// listed once, in lvkv_sst_blocks.hip.
 struct SstWriteScratch {
   uint8_t* slots;           // the compressed forms
   uint64_t* slot_off;       // block b's at slots + slot_off[b]; nullptr: at b * stride
@@ -144,9 +155,9 @@ uint64_t snappy_write_stride(uint32_t max_len);
 SstWriteScratch sst_scratch_strided(uint8_t* scratch, const uint32_t* raw_len, uint32_t nblocks,
                                     uint32_t max_len);
 // The ragged contract (lvkv_sst_write_scratch_bytes_v2): up to 255 bytes of
-// alignment, 18 bytes a block (slot_off, scan_len, clen, cst, noroom), the
-// zstd pool (sized by pool_max_len: 0 without zstd), 16 spare bytes, then the
-// slots.
+// alignment, the per-block arrays slot_off, scan_len, clen, cst, noroom, the
+// zstd pool (sized by pool_max_len: 0 without zstd) between two multiples of
+// 256, 16 spare bytes, then the slots.
 uint64_t sst_write_v2_fixed(size_t nblocks, uint32_t max_len);
 uint64_t sst_write_v2_bytes(size_t nblocks, uint64_t total_raw, uint32_t max_len);
 SstWriteScratch sst_scratch_ragged(uint8_t* scratch, uint64_t scratch_bytes, uint32_t nblocks,
@@ -197,15 +208,11 @@ struct SstFinishCtl {
   uint32_t nfilters;
   uint8_t t_type[2], t_status[2];
 };
-// Byte offsets of the call's arrays from the 256-aligned start of its scratch.
+// What the caller of the finisher needs of its scratch layout
+// (lvkv_sst_finish.hip lists it), as byte offsets from the aligned start.
 // Everything before `fixed` depends on the host's arguments alone; the data
 // blocks' ragged writer scratch takes what follows.
 struct SstFinishPlan {
-  uint64_t kx, fo, fsz, io;  // u64 a block (kx: one more)
-  uint64_t cnt, first_off, first_len, last_len, head, next_head, sep_d, klen, esz;  // u32
-  uint64_t verdict;          // u8
-  uint64_t last_key;         // max_key_len a block
-  uint64_t key_buf;          // max_key_len a lane of the bit-setting grid (keys past LDS)
   uint64_t tail_raw;         // the metaindex contents (kMetaRoom), then the index's
   uint64_t tail_scratch, tail_scratch_bytes;  // the tail's ragged writer scratch
   uint64_t index_cap;        // the longest index block of nblocks entries
@@ -223,8 +230,7 @@ struct SstFinishArgs {
   const uint32_t* raw_len;
   uint32_t nblocks;
   uint32_t key_format, bits_per_key, k, max_key_len;
-  uint8_t* base;  // the aligned scratch: SstFinishCtl, then the plan's arrays
-  SstFinishPlan plan;
+  uint8_t* base;  // the aligned scratch (scratch_base): SstFinishCtl first
   uint8_t* file;
   uint64_t cap;
   const uint64_t* hoff;  // the data blocks' handles
@@ -241,16 +247,8 @@ hipError_t launch_sst_finish(const SstFinishArgs& a, int stage, hipStream_t stre
 // Entries a workgroup resolves the chain of block starts for in LDS; the call
 // changes path with the entry count only here (one tile, several).
 constexpr uint32_t kBuildTile = 4096;
-// Byte offsets of the call's arrays from the 256-aligned start of its scratch
-// (the control words first).
-struct SstBuildPlan {
-  uint64_t ea, ed, ef, eb;                   // u64, one more than the entries
-  uint64_t lcp, next, exit, bstart;          // u32 an entry
-  uint64_t entry;                            // u32 a tile
-  uint64_t sums;                             // the scans' tile sums
-  uint64_t bytes;
-};
-SstBuildPlan sst_build_plan(size_t nentries);
+// lvkv_sst_build_blocks_scratch_bytes: the call's arrays and alignment slack.
+size_t sst_build_scratch_bytes(size_t nentries);
 struct SstBuildArgs {
   const uint8_t* keys;
   const uint64_t* key_off;
@@ -259,8 +257,7 @@ struct SstBuildArgs {
   const uint64_t* val_off;
   const uint32_t* val_len;
   uint32_t n, block_size, restart_interval, key_format;
-  uint8_t* base;  // the aligned scratch
-  SstBuildPlan plan;
+  uint8_t* scratch;  // the caller's, sst_build_scratch_bytes long
   uint8_t* raw;
   uint64_t raw_capacity;
   uint64_t* raw_off;

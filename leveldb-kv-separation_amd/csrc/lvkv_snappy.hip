@@ -20,14 +20,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "lvkv_block_scan.h"
 #include "lvkv_launch.h"
+#include "lvkv_lds_bytes.h"
 #include "lvkv_snappy.h"
 
 namespace lvkv {
 namespace {
 
-constexpr uint32_t kFrag = 1u << 16;       // kBlockSize: fragments compressed alone
+constexpr uint32_t kFrag = kSnappyFragment;  // kBlockSize: fragments compressed alone
 constexpr uint32_t kMaxTable = 1u << 14;   // kMaxHashTableSize
 constexpr uint32_t kMul = 0x1e35a7bdu;
 
@@ -54,37 +54,6 @@ __host__ __device__ __forceinline__ uint32_t table_size(uint32_t n) {
   uint32_t t = 256;
   while (t < kMaxTable && t < n) t <<= 1;
   return t;
-}
-
-// Little-endian dword at byte p of an LDS buffer (4-byte aligned base, padded
-// by 8 bytes): two aligned reads.
-__device__ __forceinline__ uint32_t ld32(const uint8_t* b, uint32_t p) {
-  const uint32_t* d = reinterpret_cast<const uint32_t*>(b + (p & ~3u));
-  return __builtin_amdgcn_alignbyte(d[1], d[0], p & 3u);
-}
-__device__ __forceinline__ uint64_t ld64(const uint8_t* b, uint32_t p) {
-  const uint32_t* d = reinterpret_cast<const uint32_t*>(b + (p & ~3u));
-  const uint32_t s = p & 3u;
-  const uint32_t lo = __builtin_amdgcn_alignbyte(d[1], d[0], s);
-  const uint32_t hi = __builtin_amdgcn_alignbyte(d[2], d[1], s);
-  return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
-// Block b's bytes [0, n) from global memory into LDS (4-aligned), zero
-// padding after them. Aligned dword loads at any source alignment: LDS
-// dword i = alignbyte of source dwords i and i+1 (the second only where it
-// holds bytes of the block, so nothing past the block's last dword is read).
-__device__ __forceinline__ void stage(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t pad,
-                                      uint32_t lane) {
-  const uint32_t mis = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(src)) & 3u;
-  const uint32_t* s = reinterpret_cast<const uint32_t*>(src - mis);
-  const uint32_t nd = (n + 3u) >> 2;
-  for (uint32_t i = lane; i < nd; i += 64) {
-    const uint32_t lo = s[i];
-    const uint32_t hi = (mis != 0 && 4u * (i + 1u) < mis + n) ? s[i + 1] : 0u;
-    reinterpret_cast<uint32_t*>(dst)[i] = __builtin_amdgcn_alignbyte(hi, lo, mis);
-  }
-  for (uint32_t i = n + lane; i < n + pad; i += 64) dst[i] = 0;  // (pad >= 3)
 }
 
 // ---- compression (snappy::RawCompress 1.1.8) ------------------------------
@@ -645,272 +614,30 @@ __global__ void __launch_bounds__(64) snappy_uncompress_big_kernel(UncompressArg
   }
 }
 
-// ---- TableBuilder::WriteBlock over a batch (table/table_builder.cc:141-209) --
-
-// A block's slot for its compressed form: room for either codec's bound,
-// rounded to 16.
-__host__ __device__ constexpr uint64_t sst_slot_bytes(uint32_t n) {
-  const uint64_t sb = snappy_bound(uint64_t{n}), zb = zstd_bound(uint64_t{n});
-  return ((sb > zb ? sb : zb) + 15u) & ~uint64_t{15};
-}
-
-// Where each block's compressed form goes: an exclusive scan of the slots
-// from `first` (the bytes before it take what a block without room writes).
-// A block whose slot would end past `cap` has no room: it is compressed as
-// an empty block into the spare bytes at 0 and reported by sst_status_kernel.
-// One workgroup, a block a thread a pass.
-__global__ void __launch_bounds__(1024) sst_slots_kernel(const uint32_t* raw_len, uint32_t n,
-                                                         uint64_t first, uint64_t cap,
-                                                         uint64_t* off, uint32_t* elen,
-                                                         uint8_t* noroom) {
-  __shared__ uint64_t wsum[17];
-  uint64_t carry = first;
-  for (uint32_t base = 0; base < n; base += 1024) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t L = i < n ? raw_len[i] : 0u;
-    const uint64_t local = i < n ? sst_slot_bytes(L) : 0u;
-    uint64_t total;
-    const uint64_t at = carry + block_scan(local, wsum, &total);
-    if (i < n) {
-      const bool room = at + local <= cap;
-      off[i] = room ? at : 0u;
-      elen[i] = room ? L : 0u;
-      noroom[i] = room ? 0 : 1;
-    }
-    carry += total;
-    __syncthreads();
-  }
-}
-
-// The verdict the caller sees, and the one the layout acts on.
-__global__ void __launch_bounds__(256) sst_status_kernel(uint8_t* cst, const uint8_t* noroom,
-                                                         uint32_t n, uint8_t* status) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  uint8_t st = LVKV_SNAPPY_OK;
-  if (cst != nullptr) {
-    st = noroom != nullptr && noroom[i] ? static_cast<uint8_t>(LVKV_SNAPPY_TOO_LARGE) : cst[i];
-    cst[i] = st;
-  }
-  status[i] = st;
-}
-
-// Which form each block keeps and where it lands: the compressed form when
-// it is smaller than raw - raw/8 (table_builder.cc:160-168), else raw with
-// type kNoCompression; handles are an exclusive scan of size + 5 (the
-// trailer, :206) from file_offset, or from *base where an earlier kernel of
-// the stream left the offset on the device. nfit (where asked for) = the
-// blocks, a prefix, that end at or before `cap`. One workgroup, 4 blocks a
-// thread a pass.
-__global__ void __launch_bounds__(1024) sst_layout_kernel(const uint32_t* raw_len,
-                                                          const uint32_t* clen, const uint8_t* cst,
-                                                          uint32_t n, uint64_t file_offset,
-                                                          uint64_t* hoff, uint32_t* hsize,
-                                                          uint8_t* type, uint64_t* end,
-                                                          uint32_t ctype, const uint64_t* base,
-                                                          uint64_t cap, uint32_t* nfit) {
-  __shared__ uint64_t wsum[17];
-  __shared__ uint32_t fit;
-  const uint32_t t = threadIdx.x;
-  if (t == 0) fit = 0;
-  uint64_t carry = base != nullptr ? *base : file_offset;
-  uint32_t mine = 0;
-  for (uint32_t base_i = 0; base_i < n; base_i += 4096) {
-    uint32_t sz[4];
-    uint8_t ty[4];
-    uint64_t local = 0;
-    for (uint32_t j = 0; j < 4; ++j) {
-      const uint32_t i = base_i + 4 * t + j;
-      sz[j] = 0;
-      ty[j] = 0;
-      if (i < n) {
-        const uint32_t L = raw_len[i];
-        const bool c = clen != nullptr && cst[i] == LVKV_SNAPPY_OK && clen[i] < L - L / 8u;
-        sz[j] = c ? clen[i] : L;
-        ty[j] = c ? static_cast<uint8_t>(ctype) : 0;
-        local += sz[j] + 5u;
-      }
-    }
-    uint64_t total;
-    uint64_t at = carry + block_scan(local, wsum, &total);
-    for (uint32_t j = 0; j < 4; ++j) {
-      const uint32_t i = base_i + 4 * t + j;
-      if (i < n) {
-        hoff[i] = at;
-        hsize[i] = sz[j];
-        type[i] = ty[j];
-        at += sz[j] + 5u;
-        if (at <= cap) ++mine;
-      }
-    }
-    carry += total;
-    __syncthreads();
-  }
-  if (nfit != nullptr) {
-    if (mine) atomicAdd(&fit, mine);
-    __syncthreads();
-    if (t == 0) *nfit = fit;
-  }
-  if (t == 0) *end = carry;
-}
-
-// WriteRawBlock's bytes but the CRC (table_builder.cc:195-204): the kept
-// contents at the handle, the type byte after them; a block whose trailer
-// would end past `cap` is left out. The masked CRC is the batch CRC kernel's
-// (lvkv_sst_fill_trailers_device) over the same handles.
-__global__ void __launch_bounds__(256) sst_place_kernel(const uint8_t* raw, const uint64_t* raw_off,
-                                                        const uint8_t* comp, const uint64_t* comp_off,
-                                                        uint64_t comp_stride, const uint64_t* hoff,
-                                                        const uint32_t* hsize, const uint8_t* type,
-                                                        uint8_t* file, uint64_t cap) {
-  const uint32_t b = blockIdx.x, t = threadIdx.x;
-  const uint32_t ty = type[b];
-  const uint32_t n = hsize[b];
-  if (hoff[b] > cap || cap - hoff[b] < uint64_t{n} + 5u) return;
-  const uint8_t* src =
-      ty ? comp + (comp_off ? comp_off[b] : b * comp_stride) : raw + raw_off[b];
-  uint8_t* dst = file + hoff[b];
-  for (uint32_t k = t; k < n; k += 256) dst[k] = src[k];
-  if (t == 0) dst[n] = static_cast<uint8_t>(ty);
-}
-
-// snappy_compress_kernel over a.nblocks blocks, a.frag_cap set: the LDS holds
-// a fragment of frag_cap bytes (16 of padding), the 256 slots of the literal
-// search and the hash table of that fragment.
-hipError_t run_snappy_compress(const CompressArgs& a, hipStream_t stream) {
-  const uint32_t in_bytes = (a.frag_cap + 16u + 15u) & ~15u;
-  const size_t lds = in_bytes + 1024u + 2u * table_size(a.frag_cap);
-  hipLaunchKernelGGL(snappy_compress_kernel, dim3(a.nblocks), dim3(64), lds, stream, a);
-  return hipGetLastError();
-}
-
-constexpr uint64_t kSstSpare = 16;  // the slot of the blocks without room
-
-uint64_t sst_v2_head(size_t nblocks) {  // off u64, elen u32, clen u32, cst u8, noroom u8
-  return (uint64_t{nblocks} * 18u + 255u) & ~uint64_t{255};
-}
-
-uint64_t sst_v2_pool(uint32_t max_len) {  // the zstd compressor's, 0 up to 20,480
-  return (zstd_compress_big_scratch(max_len) + 255u) & ~uint64_t{255};
-}
-
 }  // namespace
-
-uint64_t snappy_write_stride(uint32_t max_len) { return sst_slot_bytes(max_len); }
-
-SstWriteScratch sst_scratch_strided(uint8_t* scratch, const uint32_t* raw_len, uint32_t nblocks,
-                                    uint32_t max_len) {
-  SstWriteScratch s{};
-  s.slots = scratch;
-  s.stride = snappy_write_stride(max_len);
-  s.src_len = raw_len;
-  s.clen = reinterpret_cast<uint32_t*>(scratch + s.stride * nblocks);
-  s.cst = reinterpret_cast<uint8_t*>(s.clen + nblocks);
-  return s;
-}
-
-// The part of the v2 scratch that does not hold compressed blocks: alignment
-// slack, the per-block arrays, the zstd compressor's pool.
-uint64_t sst_write_v2_fixed(size_t nblocks, uint32_t max_len) {
-  return 256u + sst_v2_head(nblocks) + sst_v2_pool(max_len);
-}
-
-uint64_t sst_write_v2_bytes(size_t nblocks, uint64_t total_raw, uint32_t max_len) {
-  // sum of slots <= total + total / 6 (MaxCompressedLength less its constant)
-  // + 79 a block (either bound's constant + rounding)
-  return sst_write_v2_fixed(nblocks, max_len) + kSstSpare + (snappy_bound(total_raw) - 32u) +
-         uint64_t{nblocks} * 80u;
-}
-
-SstWriteScratch sst_scratch_ragged(uint8_t* scratch, uint64_t scratch_bytes, uint32_t nblocks,
-                                   uint32_t pool_max_len) {
-  SstWriteScratch s{};
-  uint8_t* base = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(scratch) + 255u) &
-                                             ~uintptr_t{255});
-  s.slot_off = reinterpret_cast<uint64_t*>(base);
-  s.scan_len = reinterpret_cast<uint32_t*>(s.slot_off + nblocks);
-  s.src_len = s.scan_len;
-  s.clen = s.scan_len + nblocks;
-  s.cst = reinterpret_cast<uint8_t*>(s.clen + nblocks);
-  s.noroom = s.cst + nblocks;
-  s.zstd_pool = base + sst_v2_head(nblocks);
-  s.slots = s.zstd_pool + sst_v2_pool(pool_max_len);
-  // (the caller checked: the slots start at least kSstSpare before the end)
-  s.slot_cap = scratch_bytes - static_cast<uint64_t>(s.slots - scratch);
-  return s;
-}
-
-// The pipeline: the slots scan (where the scratch has per-block offsets), the
-// codec, the status merge (where a status is asked for), the layout, the
-// place. An empty batch runs the layout alone, which stores end = file_offset.
-// dest (may be null): the base offset on the device and a bound on the file.
-hipError_t launch_sst_write_blocks(const uint8_t* raw, const uint64_t* raw_off,
-                                   const uint32_t* raw_len, uint32_t nblocks, int compression,
-                                   uint32_t max_len, const SstWriteScratch& s, uint8_t* file,
-                                   uint64_t file_offset, uint64_t* hoff, uint32_t* hsize,
-                                   uint8_t* type, uint64_t* end, int zstd_level, uint8_t* status,
-                                   hipStream_t stream, const SstWriteDest* dest) {
-  const bool any = nblocks != 0;
-  const uint64_t* base = dest != nullptr ? dest->base : nullptr;
-  const uint64_t cap = dest != nullptr ? dest->cap : ~uint64_t{0};
-  uint32_t* nfit = dest != nullptr ? dest->nfit : nullptr;
-  if (any && compression != 0) {
-    if (s.slot_off != nullptr)
-      hipLaunchKernelGGL(sst_slots_kernel, dim3(1), dim3(1024), 0, stream, raw_len, nblocks,
-                         kSstSpare, s.slot_cap, s.slot_off, s.scan_len, s.noroom);
-    hipError_t e;
-    if (compression == 1) {
-      // a stride was sized from max_len; a slot of its own holds any block's bound
-      const uint32_t frag_cap = s.slot_off != nullptr ? kFrag : max(16u, min(max_len, kFrag));
-      e = run_snappy_compress(CompressArgs{raw, raw_off, s.src_len, s.slots, s.slot_off, s.clen,
-                                           s.cst, nblocks, frag_cap, s.stride, max_len},
-                              stream);
-    } else {  // kZstdCompression (one kernel when max_len <= 20,480)
-      e = launch_zstd_compress_big(raw, raw_off, s.src_len, s.slots, s.slot_off, s.clen, s.cst,
-                                   nblocks, max_len, zstd_level, s.stride, s.zstd_pool, stream);
-    }
-    if (e != hipSuccess) return e;
-  }
-  if (any && status != nullptr)
-    hipLaunchKernelGGL(sst_status_kernel, dim3((nblocks + 255u) / 256u), dim3(256), 0, stream,
-                       s.cst, s.noroom, nblocks, status);
-  hipLaunchKernelGGL(sst_layout_kernel, dim3(1), dim3(1024), 0, stream, raw_len, s.clen, s.cst,
-                     nblocks, file_offset, hoff, hsize, type, end,
-                     static_cast<uint32_t>(compression == 2 ? 2 : 1), base, cap, nfit);
-  if (any)
-    hipLaunchKernelGGL(sst_place_kernel, dim3(nblocks), dim3(256), 0, stream, raw, raw_off,
-                       s.slots, s.slot_off, s.stride, hoff, hsize, type, file, cap);
-  return hipGetLastError();
-}
-
-hipError_t launch_sst_read_blocks(const uint8_t* file, const uint64_t* hoff, const uint32_t* hsize,
-                                  uint32_t nblocks, uint8_t* out, const uint64_t* out_off,
-                                  const uint32_t* out_cap, uint32_t* out_len, uint8_t* status,
-                                  const uint8_t* vstatus, uint32_t max_ulen, hipStream_t stream) {
-  UncompressArgs a{file, hoff, hsize, out, out_off, out_cap, out_len, status, nblocks, 0, 1,
-                   vstatus};
-  a.out_cap = max(16u, max_ulen);
-  const size_t lds = ((snappy_bound(a.out_cap) + 16u + 15u) & ~15u) + ((a.out_cap + 15u) & ~15u);
-  hipLaunchKernelGGL(snappy_uncompress_kernel, dim3(nblocks), dim3(64), lds, stream, a);
-  hipLaunchKernelGGL(snappy_uncompress_big_kernel, dim3((nblocks + kBigChunk - 1u) / kBigChunk),
-                     dim3(64), kBigWin + 16u + kBigRing, stream, a);
-  return hipGetLastError();
-}
 
 hipError_t launch_snappy_compress(const uint8_t* src, const uint64_t* src_off,
                                   const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
                                   uint32_t* dst_len, uint8_t* status, uint32_t nblocks,
-                                  uint32_t max_len, hipStream_t stream) {
+                                  uint32_t max_len, uint64_t dst_stride, hipStream_t stream) {
+  // the LDS holds a fragment of frag_cap bytes (16 of padding), the 256 slots
+  // of the literal search and the hash table of that fragment
   const uint32_t frag_cap = max(16u, min(max_len, kFrag));
-  return run_snappy_compress(
-      CompressArgs{src, src_off, src_len, dst, dst_off, dst_len, status, nblocks, frag_cap}, stream);
+  const CompressArgs a{src,    src_off, src_len,  dst,        dst_off, dst_len,
+                       status, nblocks, frag_cap, dst_stride, max_len};
+  const uint32_t in_bytes = (frag_cap + 16u + 15u) & ~15u;
+  const size_t lds = in_bytes + 1024u + 2u * table_size(frag_cap);
+  hipLaunchKernelGGL(snappy_compress_kernel, dim3(nblocks), dim3(64), lds, stream, a);
+  return hipGetLastError();
 }
 
 hipError_t launch_snappy_uncompress(const uint8_t* src, const uint64_t* src_off,
                                     const uint32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
                                     const uint32_t* dst_cap, uint32_t* out_len, uint8_t* status,
-                                    uint32_t nblocks, uint32_t max_ulen, hipStream_t stream) {
-  UncompressArgs a{src, src_off, src_len, dst, dst_off, dst_cap, out_len, status, nblocks, 0};
+                                    uint32_t nblocks, uint32_t max_ulen, uint32_t block_mode,
+                                    const uint8_t* vstatus, hipStream_t stream) {
+  UncompressArgs a{src,    src_off, src_len, dst, dst_off,    dst_cap, out_len,
+                   status, nblocks, 0,       block_mode, vstatus};
   a.out_cap = dst_cap == nullptr ? 0u : max(16u, max_ulen);
   const size_t lds = dst_cap == nullptr ? 16u
                                         : ((snappy_bound(a.out_cap) + 16u + 15u) & ~15u) +

@@ -33,7 +33,9 @@
 
 #include "lvkv_block_scan.h"
 #include "lvkv_launch.h"
+#include "lvkv_scratch.h"
 #include "lvkv_snappy.h"
+#include "lvkv_table_format.h"
 
 namespace lvkv {
 namespace {
@@ -56,7 +58,7 @@ struct Ctl {
   unsigned long long max_block_len;
   uint64_t last_len;   // the last block's contents
 };
-static_assert(sizeof(Ctl) <= 256, "the control words' room");
+static_assert(sizeof(Ctl) <= kScratchAlign, "the control words' room");
 
 struct Dev {
   const uint8_t* keys;
@@ -78,32 +80,6 @@ struct Dev {
   uint32_t* raw_len;
   lvkv_sst_build_report* report;
 };
-
-__device__ __forceinline__ uint32_t varint_len(uint32_t v) {
-  return 1u + (v >= (1u << 7)) + (v >= (1u << 14)) + (v >= (1u << 21)) + (v >= (1u << 28));
-}
-
-__device__ __forceinline__ uint8_t* put_varint(uint8_t* p, uint32_t v) {
-  while (v >= 128u) {
-    *p++ = static_cast<uint8_t>(v | 128u);
-    v >>= 7;
-  }
-  *p++ = static_cast<uint8_t>(v);
-  return p;
-}
-
-__device__ __forceinline__ void put_le32(uint8_t* p, uint32_t v) {
-  p[0] = static_cast<uint8_t>(v);
-  p[1] = static_cast<uint8_t>(v >> 8);
-  p[2] = static_cast<uint8_t>(v >> 16);
-  p[3] = static_cast<uint8_t>(v >> 24);
-}
-
-__device__ __forceinline__ uint64_t ld_le64(const uint8_t* p) {
-  uint64_t v = 0;
-  for (int b = 7; b >= 0; --b) v = (v << 8) | p[b];
-  return v;
-}
 
 // Entry i's place in residue-class order.
 __device__ __forceinline__ uint64_t perm(const Dev& d, uint32_t i) {
@@ -246,16 +222,8 @@ __global__ void __launch_bounds__(1024) scan_reduce_kernel(ScanArgs s) {
 __global__ void __launch_bounds__(1024) scan_sums_kernel(ScanArgs s) {
   __shared__ uint64_t wsum[17];
   uint64_t* sums = s.sums + uint64_t{blockIdx.x} * s.tiles;
-  uint64_t carry = 0;
-  for (uint32_t at = 0; at < s.tiles; at += 1024u) {
-    const uint32_t t = at + threadIdx.x;
-    const uint64_t v = t < s.tiles ? sums[t] : 0;
-    uint64_t total;
-    const uint64_t ex = block_scan(v, wsum, &total);
-    if (t < s.tiles) sums[t] = carry + ex;
-    carry += total;
-    __syncthreads();
-  }
+  block_scan_carry(s.tiles, 0, wsum, [&](uint32_t t) { return sums[t]; },
+                   [&](uint32_t t, uint64_t at) { sums[t] = at; });
 }
 
 __global__ void __launch_bounds__(1024) scan_apply_kernel(ScanArgs s) {
@@ -451,17 +419,15 @@ __global__ void __launch_bounds__(256) build_write_kernel(Dev d) {
   if (restart && sub == 1) {
     const uint32_t e = d.next[s];
     uint8_t* const restarts = block + ent_off(d, s, e);
-    put_le32(restarts + 4ull * (at / d.restart), static_cast<uint32_t>(off));
+    st_le32(restarts + 4ull * (at / d.restart), static_cast<uint32_t>(off));
     if (at == 0) {
       const uint32_t count = (e - 1u - s) / d.restart + 1u;
-      put_le32(restarts + 4ull * count, count);
+      st_le32(restarts + 4ull * count, count);
       d.raw_off[b] = d.eb[b];
       d.raw_len[b] = static_cast<uint32_t>(ent_off(d, s, e)) + 4u * count + 4u;
     }
   }
 }
-
-uint64_t up16(uint64_t v) { return (v + 15u) & ~uint64_t{15}; }
 
 hipError_t scan(uint64_t* a0, uint64_t* a1, uint64_t* sums, uint32_t n, hipStream_t stream) {
   ScanArgs s{};
@@ -477,29 +443,29 @@ hipError_t scan(uint64_t* a0, uint64_t* a1, uint64_t* sums, uint32_t n, hipStrea
   return hipGetLastError();
 }
 
+// The call's scratch, listed once: the control words, then the arrays, each
+// rounded up to 16 bytes. Returns the bytes from `base` (null: sizing only).
+uint64_t carve(Dev& d, uint8_t* base, uint64_t n) {
+  Carver c(base);
+  d.ctl = c.take<Ctl>(1, kScratchAlign);
+  d.ea = c.take<uint64_t>(n + 1, 16);
+  d.ed = c.take<uint64_t>(n + 1, 16);
+  d.ef = c.take<uint64_t>(n + 1, 16);
+  d.eb = c.take<uint64_t>(n + 1, 16);
+  d.lcp = c.take<uint32_t>(n, 16);
+  d.next = c.take<uint32_t>(n, 16);
+  d.exit = c.take<uint32_t>(n, 16);
+  d.bstart = c.take<uint32_t>(n, 16);
+  d.entry = c.take<uint32_t>((n + kBuildTile - 1) / kBuildTile, 16);
+  d.sums = c.take<uint64_t>(2 * ((n + kScanTile - 1) / kScanTile), 16);  // the scans' tile sums
+  return c.bytes();
+}
+
 }  // namespace
 
-SstBuildPlan sst_build_plan(size_t nentries) {
-  const uint64_t n = nentries;
-  SstBuildPlan p{};
-  uint64_t at = 256;  // Ctl
-  auto take = [&at](uint64_t bytes) {
-    const uint64_t here = at;
-    at += up16(bytes);
-    return here;
-  };
-  p.ea = take(8 * (n + 1));
-  p.ed = take(8 * (n + 1));
-  p.ef = take(8 * (n + 1));
-  p.eb = take(8 * (n + 1));
-  p.lcp = take(4 * n);
-  p.next = take(4 * n);
-  p.exit = take(4 * n);
-  p.bstart = take(4 * n);
-  p.entry = take(4 * ((n + kBuildTile - 1) / kBuildTile));
-  p.sums = take(8 * 2 * ((n + kScanTile - 1) / kScanTile));
-  p.bytes = at;
-  return p;
+size_t sst_build_scratch_bytes(size_t nentries) {
+  Dev d{};
+  return kScratchAlign + carve(d, nullptr, nentries);  // alignment slack
 }
 
 hipError_t launch_sst_build(const SstBuildArgs& a, hipStream_t stream) {
@@ -520,19 +486,7 @@ hipError_t launch_sst_build(const SstBuildArgs& a, hipStream_t stream) {
   d.nq = a.n / a.restart_interval;
   d.nr = a.n % a.restart_interval;
   d.block_size = a.block_size;
-  uint8_t* const base = a.base;
-  const SstBuildPlan& p = a.plan;
-  d.ctl = reinterpret_cast<Ctl*>(base);
-  d.ea = reinterpret_cast<uint64_t*>(base + p.ea);
-  d.ed = reinterpret_cast<uint64_t*>(base + p.ed);
-  d.ef = reinterpret_cast<uint64_t*>(base + p.ef);
-  d.eb = reinterpret_cast<uint64_t*>(base + p.eb);
-  d.lcp = reinterpret_cast<uint32_t*>(base + p.lcp);
-  d.next = reinterpret_cast<uint32_t*>(base + p.next);
-  d.exit = reinterpret_cast<uint32_t*>(base + p.exit);
-  d.bstart = reinterpret_cast<uint32_t*>(base + p.bstart);
-  d.entry = reinterpret_cast<uint32_t*>(base + p.entry);
-  d.sums = reinterpret_cast<uint64_t*>(base + p.sums);
+  carve(d, scratch_base(a.scratch), a.n);
   d.raw = a.raw;
   d.raw_cap = a.raw_capacity;
   d.max_blocks = a.max_blocks;

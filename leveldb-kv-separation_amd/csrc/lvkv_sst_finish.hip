@@ -31,7 +31,9 @@
 
 #include "lvkv_block_scan.h"
 #include "lvkv_launch.h"
+#include "lvkv_scratch.h"
 #include "lvkv_snappy.h"
+#include "lvkv_table_format.h"
 
 namespace lvkv {
 namespace {
@@ -43,9 +45,6 @@ constexpr uint32_t kBitsGroups = 256;    // workgroups of the bit-setting grid w
 constexpr uint64_t kNowhere = uint64_t{1} << 62;  // a base offset no capacity reaches
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr uint32_t kFlagBad = 1, kFlagLong = 2;
-constexpr uint32_t kFilterBaseLg = 11;   // table/filter_block.cc
-
-uint64_t up16(uint64_t v) { return (v + 15u) & ~uint64_t{15}; }
 
 // The arguments as the kernels see them: typed pointers into the scratch.
 struct Dev {
@@ -64,113 +63,6 @@ struct Dev {
   const uint32_t* hsize;
   lvkv_sst_table_report* report;
 };
-
-__device__ __forceinline__ uint32_t ld_le32(const uint8_t* p) {
-  return static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8) |
-         (static_cast<uint32_t>(p[2]) << 16) | (static_cast<uint32_t>(p[3]) << 24);
-}
-
-__device__ __forceinline__ void st_le32(uint8_t* p, uint32_t v) {
-  for (int k = 0; k < 4; ++k) p[k] = static_cast<uint8_t>(v >> (8 * k));
-}
-
-// GetVarint32Ptr (util/coding.cc) over [p, limit): bytes consumed, 0 on
-// failure (as get_varint of lvkv_sst_table.hip).
-__device__ __forceinline__ uint32_t get_varint32(const uint8_t* p, const uint8_t* limit,
-                                                 uint32_t* v) {
-  uint32_t result = 0, i = 0;
-  for (uint32_t shift = 0; shift <= 28 && p + i < limit; shift += 7, ++i) {
-    const uint32_t b = p[i];
-    if (b & 128) {
-      result |= (b & 127) << shift;
-    } else {
-      *v = result | (b << shift);
-      return i + 1;
-    }
-  }
-  return 0;
-}
-
-// DecodeEntry (table/block.cc:55-75) over [p, limit): the key delta, or
-// nullptr when a varint or the entry's bytes run past limit.
-__device__ __forceinline__ const uint8_t* decode_entry(const uint8_t* p, const uint8_t* limit,
-                                                       uint32_t* shared, uint32_t* non_shared,
-                                                       uint32_t* value_len) {
-  if (limit - p < 3) return nullptr;
-  uint32_t n;
-  if ((n = get_varint32(p, limit, shared)) == 0) return nullptr;
-  p += n;
-  if ((n = get_varint32(p, limit, non_shared)) == 0) return nullptr;
-  p += n;
-  if ((n = get_varint32(p, limit, value_len)) == 0) return nullptr;
-  p += n;
-  if (static_cast<uint64_t>(limit - p) < static_cast<uint64_t>(*non_shared) + *value_len)
-    return nullptr;
-  return p;
-}
-
-__device__ __forceinline__ uint32_t varint_len(uint64_t v) {
-  uint32_t n = 1;
-  while (v >= 128) {
-    v >>= 7;
-    ++n;
-  }
-  return n;
-}
-
-__device__ __forceinline__ uint32_t put_varint(uint8_t* p, uint64_t v) {
-  uint32_t n = 0;
-  while (v >= 128) {
-    p[n++] = static_cast<uint8_t>(v | 128);
-    v >>= 7;
-  }
-  p[n++] = static_cast<uint8_t>(v);
-  return n;
-}
-
-// The restart array of a block of L bytes (table/block.cc:28-45): false when
-// the count does not fit; else the count and where the entries end.
-__device__ __forceinline__ bool block_restarts(const uint8_t* p, uint32_t L, uint32_t* nr,
-                                               uint32_t* limit) {
-  if (L < 8) return false;  // (a count and at least one restart)
-  const uint32_t c = ld_le32(p + L - 4);
-  if (c == 0 || c > (L - 4) / 4) return false;
-  *nr = c;
-  *limit = L - 4 - 4 * c;
-  return true;
-}
-
-// Run r of a block: [*s, *e) of the entries; false when the restart offsets
-// do not delimit a run inside them (BlockBuilder's are increasing from 0, and
-// a run ends where the next begins).
-__device__ __forceinline__ bool block_run(const uint8_t* p, uint32_t nr, uint32_t limit, uint32_t r,
-                                          uint32_t* s, uint32_t* e) {
-  const uint8_t* ra = p + limit;
-  *s = ld_le32(ra + 4 * r);
-  *e = r + 1 < nr ? ld_le32(ra + 4 * (r + 1)) : limit;
-  return (r != 0 || *s == 0) && *s < *e && *e <= limit;
-}
-
-// Hash (util/hash.cc) with BloomHash's seed (util/bloom.cc:15).
-__device__ __forceinline__ uint32_t bloom_hash(const uint8_t* d, uint32_t n) {
-  const uint32_t m = 0xc6a4a793u;
-  uint32_t h = 0xbc9f1d34u ^ (n * m);
-  uint32_t i = 0;
-  for (; i + 4 <= n; i += 4) {
-    h += ld_le32(d + i);
-    h *= m;
-    h ^= h >> 16;
-  }
-  const uint32_t rem = n - i;
-  if (rem == 3) h += static_cast<uint32_t>(d[i + 2]) << 16;
-  if (rem >= 2) h += static_cast<uint32_t>(d[i + 1]) << 8;
-  if (rem >= 1) {
-    h += d[i];
-    h *= m;
-    h ^= h >> 24;
-  }
-  return h;
-}
 
 __global__ void finish_init_kernel(SstFinishCtl* c) {
   if (threadIdx.x != 0) return;
@@ -253,16 +145,8 @@ __global__ void __launch_bounds__(1024) finish_layout_kernel(Dev d) {
   __shared__ uint64_t wsum[17];
   const uint32_t t = threadIdx.x, n = d.n;
   SstFinishCtl* c = d.ctl;
-  uint64_t carry = 0;
-  for (uint32_t base = 0; base < n; base += 1024) {
-    const uint32_t i = base + t;
-    uint64_t total;
-    const uint64_t at = carry + block_scan(i < n ? d.cnt[i] : 0u, wsum, &total);
-    if (i < n) d.kx[i] = at;
-    carry += total;
-    __syncthreads();
-  }
-  const uint64_t nkeys = carry;
+  const uint64_t nkeys = block_scan_carry(n, 0, wsum, [&](uint32_t i) { return d.cnt[i]; },
+                                          [&](uint32_t i, uint64_t at) { d.kx[i] = at; });
   if (t == 0) d.kx[n] = nkeys;
   __threadfence();
   __syncthreads();
@@ -270,36 +154,28 @@ __global__ void __launch_bounds__(1024) finish_layout_kernel(Dev d) {
   bool ok = c->first_bad == kNone && c->nfit_data == n && data_end <= d.cap;
   uint64_t fbytes = 0, fsize = 0, nf = 0;
   if (ok && d.bits_per_key != 0) {
-    carry = 0;
-    for (uint32_t base = 0; base < n; base += 1024) {
-      const uint32_t i = base + t;
-      uint64_t size = 0;
-      bool head = false;
-      if (i < n) {
-        const uint64_t f = d.hoff[i] >> kFilterBaseLg;
-        head = i == 0 || (d.hoff[i - 1] >> kFilterBaseLg) != f;
-        if (head) {
-          // (a sound block and its trailer take 16 bytes or more: at most 128
-          // blocks share a filter)
-          uint32_t j = i;
-          do d.head[j++] = i;
-          while (j < n && (d.hoff[j] >> kFilterBaseLg) == f);
-          const uint64_t keys = d.kx[j] - d.kx[i];
-          uint64_t bits = keys * d.bits_per_key;
-          if (bits < 64) bits = 64;
-          size = (bits + 7) / 8;
-          d.next_head[i] = j;
-          d.fsz[i] = size;
-          size += 1;  // the probe count
-        }
-      }
-      uint64_t total;
-      const uint64_t at = carry + block_scan(size, wsum, &total);
+    // a head's value: its filter's bytes and the probe count; 0 for the rest
+    bool head = false;
+    auto filter_size = [&](uint32_t i) -> uint64_t {
+      const uint64_t f = d.hoff[i] >> kFilterBaseLg;
+      head = i == 0 || (d.hoff[i - 1] >> kFilterBaseLg) != f;
+      if (!head) return 0;
+      // (a sound block and its trailer take 16 bytes or more: at most 128
+      // blocks share a filter)
+      uint32_t j = i;
+      do d.head[j++] = i;
+      while (j < n && (d.hoff[j] >> kFilterBaseLg) == f);
+      const uint64_t keys = d.kx[j] - d.kx[i];
+      uint64_t bits = keys * d.bits_per_key;
+      if (bits < 64) bits = 64;
+      const uint64_t size = (bits + 7) / 8;
+      d.next_head[i] = j;
+      d.fsz[i] = size;
+      return size + 1;
+    };
+    fbytes = block_scan_carry(n, 0, wsum, filter_size, [&](uint32_t i, uint64_t at) {
       if (head) d.fo[i] = at;
-      carry += total;
-      __syncthreads();
-    }
-    fbytes = carry;
+    });
     // filters emitted: up to the last block's own, and the empty ones a long
     // last block leaves behind it
     if (n != 0) {
@@ -452,15 +328,8 @@ __global__ void __launch_bounds__(1024) finish_index_layout_kernel(Dev d) {
   const uint32_t t = threadIdx.x, n = d.n;
   SstFinishCtl* c = d.ctl;
   if (!c->ok) return;  // (the lengths stay 0, the base nowhere)
-  uint64_t carry = 0;
-  for (uint32_t base = 0; base < n; base += 1024) {
-    const uint32_t i = base + t;
-    uint64_t total;
-    const uint64_t at = carry + block_scan(i < n ? d.esz[i] : 0u, wsum, &total);
-    if (i < n) d.io[i] = at;
-    carry += total;
-    __syncthreads();
-  }
+  const uint64_t carry = block_scan_carry(n, 0, wsum, [&](uint32_t i) { return d.esz[i]; },
+                                          [&](uint32_t i, uint64_t at) { d.io[i] = at; });
   if (t != 0) return;
   c->index_entries = carry;
   const uint32_t restarts = n != 0 ? n : 1u;  // BlockBuilder starts with one
@@ -477,8 +346,7 @@ __global__ void __launch_bounds__(1024) finish_index_layout_kernel(Dev d) {
     m[len++] = static_cast<uint8_t>(klen);
     m[len++] = static_cast<uint8_t>(vlen);
     for (uint32_t i = 0; i < klen; ++i) m[len++] = static_cast<uint8_t>(name[i]);
-    len += put_varint(m + len, c->data_end);
-    len += put_varint(m + len, c->filter_size);
+    len = static_cast<uint32_t>(put_varint(put_varint(m + len, c->data_end), c->filter_size) - m);
   }
   st_le32(m + len, 0);
   st_le32(m + len + 4, 1);
@@ -499,7 +367,7 @@ __global__ void __launch_bounds__(256) finish_index_write_kernel(Dev d) {
   uint8_t* p = d.index + off;
   const uint32_t vlen = varint_len(d.hoff[b]) + varint_len(d.hsize[b]);
   *p++ = 0;
-  p += put_varint(p, klen);
+  p = put_varint(p, klen);
   *p++ = static_cast<uint8_t>(vlen);
   if (at == kNone) {
     for (uint32_t i = 0; i < klen; ++i) p[i] = a[i];
@@ -512,8 +380,8 @@ __global__ void __launch_bounds__(256) finish_index_write_kernel(Dev d) {
     }
   }
   p += klen;
-  p += put_varint(p, d.hoff[b]);
-  p += put_varint(p, d.hsize[b]);
+  p = put_varint(p, d.hoff[b]);
+  p = put_varint(p, d.hsize[b]);
   st_le32(d.index + c->index_entries + 4 * uint64_t{b}, static_cast<uint32_t>(off));
 }
 
@@ -530,7 +398,7 @@ __global__ void finish_report_kernel(Dev d) {
   if (c->first_bad != kNone) {
     r.status = d.verdict[c->first_bad];
     r.first_bad_block = c->first_bad;
-  } else if (!c->ok || c->nfit_tail != 2 || c->tail_end > d.cap || d.cap - c->tail_end < 48) {
+  } else if (!c->ok || c->nfit_tail != 2 || c->tail_end > d.cap || d.cap - c->tail_end < kFooterLen) {
     r.status = LVKV_TABLE_CAPACITY;
   }
   if (c->ok) {
@@ -550,56 +418,15 @@ __global__ void finish_report_kernel(Dev d) {
   }
   if (r.status == LVKV_TABLE_OK) {
     uint8_t* f = d.file + c->tail_end;
-    uint32_t n = put_varint(f, r.meta_offset);
-    n += put_varint(f + n, r.meta_size);
-    n += put_varint(f + n, r.index_offset);
-    n += put_varint(f + n, r.index_size);
-    for (; n < 40; ++n) f[n] = 0;
-    const uint64_t magic = 0xdb4775248b80fb57ull;
-    for (uint32_t i = 0; i < 8; ++i) f[40 + i] = static_cast<uint8_t>(magic >> (8 * i));
-    r.file_size = c->tail_end + 48;
+    uint8_t* const magic = f + kFooterLen - 8;
+    uint8_t* p = put_varint(put_varint(f, r.meta_offset), r.meta_size);
+    p = put_varint(put_varint(p, r.index_offset), r.index_size);
+    while (p < magic) *p++ = 0;
+    for (uint32_t i = 0; i < 8; ++i) magic[i] = static_cast<uint8_t>(kTableMagic >> (8 * i));
+    r.file_size = c->tail_end + kFooterLen;
   }
   c->tail_count = c->ok ? (filter ? 1u : 0u) + c->nfit_tail : 0u;
   *d.report = r;
-}
-
-Dev dev_args(const SstFinishArgs& a) {
-  const SstFinishPlan& p = a.plan;
-  uint8_t* s = a.base;
-  Dev d{};
-  d.raw = a.raw;
-  d.raw_off = a.raw_off;
-  d.raw_len = a.raw_len;
-  d.n = a.nblocks;
-  d.key_format = a.key_format;
-  d.bits_per_key = a.bits_per_key;
-  d.k = a.k;
-  d.max_key_len = a.max_key_len;
-  d.ctl = reinterpret_cast<SstFinishCtl*>(s);
-  d.kx = reinterpret_cast<uint64_t*>(s + p.kx);
-  d.fo = reinterpret_cast<uint64_t*>(s + p.fo);
-  d.fsz = reinterpret_cast<uint64_t*>(s + p.fsz);
-  d.io = reinterpret_cast<uint64_t*>(s + p.io);
-  d.cnt = reinterpret_cast<uint32_t*>(s + p.cnt);
-  d.first_off = reinterpret_cast<uint32_t*>(s + p.first_off);
-  d.first_len = reinterpret_cast<uint32_t*>(s + p.first_len);
-  d.last_len = reinterpret_cast<uint32_t*>(s + p.last_len);
-  d.head = reinterpret_cast<uint32_t*>(s + p.head);
-  d.next_head = reinterpret_cast<uint32_t*>(s + p.next_head);
-  d.sep_d = reinterpret_cast<uint32_t*>(s + p.sep_d);
-  d.klen = reinterpret_cast<uint32_t*>(s + p.klen);
-  d.esz = reinterpret_cast<uint32_t*>(s + p.esz);
-  d.verdict = s + p.verdict;
-  d.last_key = s + p.last_key;
-  d.key_buf = s + p.key_buf;
-  d.meta = s + p.tail_raw;
-  d.index = s + p.tail_raw + kSstMetaRoom;
-  d.file = a.file;
-  d.cap = a.cap;
-  d.hoff = a.hoff;
-  d.hsize = a.hsize;
-  d.report = a.report;
-  return d;
 }
 
 }  // namespace
@@ -628,56 +455,83 @@ uint64_t sst_write_v2_envelope(size_t nblocks, uint64_t total_raw, uint32_t max_
   return v > p ? v : p;
 }
 
-SstFinishPlan sst_finish_plan(size_t nblocks, uint32_t max_key_len, int filter_bits_per_key) {
-  static_assert(sizeof(SstFinishCtl) <= 256, "the control words' room");
-  const uint64_t n = nblocks;
+namespace {
+
+// The call's scratch, listed once: the control words, the per-block arrays
+// and the key buffers, each rounded up to 16 bytes, the tail's contents, and
+// between two multiples of 256 the tail's ragged writer scratch. What the
+// caller needs of the layout besides the kernels' pointers is returned
+// (base null: sizing only).
+SstFinishPlan carve(Dev& d, uint8_t* base, uint64_t n, uint32_t max_key_len,
+                    int filter_bits_per_key) {
+  static_assert(sizeof(SstFinishCtl) <= kScratchAlign, "the control words' room");
+  Carver c(base);
   SstFinishPlan p{};
-  uint64_t at = 256;
-  auto take = [&at](uint64_t bytes) {
-    const uint64_t here = at;
-    at += up16(bytes);
-    return here;
-  };
-  p.kx = take(8 * (n + 1));
-  p.fo = take(8 * n);
-  p.fsz = take(8 * n);
-  p.io = take(8 * n);
-  p.cnt = take(4 * n);
-  p.first_off = take(4 * n);
-  p.first_len = take(4 * n);
-  p.last_len = take(4 * n);
-  p.head = take(4 * n);
-  p.next_head = take(4 * n);
-  p.sep_d = take(4 * n);
-  p.klen = take(4 * n);
-  p.esz = take(4 * n);
-  p.verdict = take(n);
-  p.last_key = take(n * max_key_len);
+  d.ctl = c.take<SstFinishCtl>(1, kScratchAlign);
+  d.kx = c.take<uint64_t>(n + 1, 16);
+  d.fo = c.take<uint64_t>(n, 16);
+  d.fsz = c.take<uint64_t>(n, 16);
+  d.io = c.take<uint64_t>(n, 16);
+  d.cnt = c.take<uint32_t>(n, 16);
+  d.first_off = c.take<uint32_t>(n, 16);
+  d.first_len = c.take<uint32_t>(n, 16);
+  d.last_len = c.take<uint32_t>(n, 16);
+  d.head = c.take<uint32_t>(n, 16);
+  d.next_head = c.take<uint32_t>(n, 16);
+  d.sep_d = c.take<uint32_t>(n, 16);
+  d.klen = c.take<uint32_t>(n, 16);
+  d.esz = c.take<uint32_t>(n, 16);
+  d.verdict = c.take<uint8_t>(n, 16);
+  d.last_key = c.take<uint8_t>(n * max_key_len, 16);
   // the bit-setting grid: a wave for every 64 / kLanes blocks and its keys in
   // LDS, or kBitsGroups waves that loop, each lane's key in the scratch
   const uint64_t waves = n != 0 ? (n + kBlocksPerWave - 1) / kBlocksPerWave : 1;
   const bool hbm_keys = filter_bits_per_key > 0 && max_key_len > kLdsKeyMax;
   p.bits_groups = static_cast<uint32_t>(hbm_keys && waves > kBitsGroups ? kBitsGroups : waves);
-  p.key_buf = take(hbm_keys ? uint64_t{p.bits_groups} * 64u * max_key_len : 0);
+  d.key_buf = c.take<uint8_t>(hbm_keys ? uint64_t{p.bits_groups} * 64u * max_key_len : 0, 16);
   // an index entry: shared, the key's length (a varint32), the value's, the
   // key, two varint64 of a handle whose size is a u32, its restart; then the
   // count (and the one restart of a block without entries)
   p.index_cap = n * (uint64_t{max_key_len} + 1 + 5 + 1 + 10 + 5 + 4) + 8;
-  p.tail_raw = take(kSstMetaRoom + p.index_cap);
+  p.tail_raw = c.bytes();
+  static_assert(kSstMetaRoom % 16 == 0, "the index contents follow the metaindex's room");
+  d.meta = c.take<uint8_t>(kSstMetaRoom, 16);
+  d.index = c.take<uint8_t>(p.index_cap, 16);
   const uint64_t big = 128u << 10;
   p.tail_max_len = static_cast<uint32_t>(p.index_cap < big ? p.index_cap : big);
   if (p.tail_max_len < kSstMetaRoom) p.tail_max_len = kSstMetaRoom;
-  at = (at + 255u) & ~uint64_t{255};
-  p.tail_scratch = at;
   p.tail_scratch_bytes = sst_write_v2_envelope(2, kSstMetaRoom + p.index_cap, p.tail_max_len);
-  at += (p.tail_scratch_bytes + 255u) & ~uint64_t{255};
-  p.fixed = at;
+  c.align(kScratchAlign);
+  p.tail_scratch = c.bytes();
+  c.take<uint8_t>(p.tail_scratch_bytes, kScratchAlign);
+  p.fixed = c.bytes();
   return p;
 }
 
+}  // namespace
+
+SstFinishPlan sst_finish_plan(size_t nblocks, uint32_t max_key_len, int filter_bits_per_key) {
+  Dev d{};
+  return carve(d, nullptr, nblocks, max_key_len, filter_bits_per_key);
+}
+
 hipError_t launch_sst_finish(const SstFinishArgs& a, int stage, hipStream_t stream) {
-  const Dev d = dev_args(a);
   const uint32_t n = a.nblocks;
+  Dev d{};
+  d.raw = a.raw;
+  d.raw_off = a.raw_off;
+  d.raw_len = a.raw_len;
+  d.n = n;
+  d.key_format = a.key_format;
+  d.bits_per_key = a.bits_per_key;
+  d.k = a.k;
+  d.max_key_len = a.max_key_len;
+  d.file = a.file;
+  d.cap = a.cap;
+  d.hoff = a.hoff;
+  d.hsize = a.hsize;
+  d.report = a.report;
+  const SstFinishPlan plan = carve(d, a.base, n, a.max_key_len, static_cast<int>(a.bits_per_key));
   const uint32_t per_block = n != 0 ? (n + 255u) / 256u : 1u;
   if (stage == 0) {
     hipLaunchKernelGGL(finish_init_kernel, dim3(1), dim3(64), 0, stream, d.ctl);
@@ -689,7 +543,7 @@ hipError_t launch_sst_finish(const SstFinishArgs& a, int stage, hipStream_t stre
     if (a.bits_per_key != 0) {
       if (n != 0) {
         hipLaunchKernelGGL(finish_zero_kernel, dim3(512), dim3(256), 0, stream, d);
-        hipLaunchKernelGGL(finish_bits_kernel, dim3(a.plan.bits_groups), dim3(64),
+        hipLaunchKernelGGL(finish_bits_kernel, dim3(plan.bits_groups), dim3(64),
                            a.max_key_len <= kLdsKeyMax ? 64u * a.max_key_len : 0u, stream, d);
       }
       hipLaunchKernelGGL(finish_filter_tail_kernel, dim3(per_block), dim3(256), 0, stream, d);

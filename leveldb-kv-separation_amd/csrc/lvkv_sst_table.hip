@@ -54,13 +54,12 @@
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
 #include "lvkv_launch.h"
+#include "lvkv_table_format.h"
 
 namespace lvkv {
 
 namespace {
 
-constexpr uint64_t kTableMagic = 0xdb4775248b80fb57ull;  // table/format.h:76
-constexpr uint64_t kFooterLen = 48;  // table/format.h:53 (2 * 20 + 8)
 constexpr uint64_t kTrailer = 5;     // table/format.h:79
 constexpr uint32_t kMetaStage = 2048;                // metaindex staged in LDS up to this
 constexpr uint32_t kIndexStage = kCompactLdsBytes;   // index staged in the (spent) image
@@ -88,35 +87,12 @@ __device__ __forceinline__ Table table_of(const uint8_t* file, const uint64_t* t
   return x;
 }
 
-__device__ __forceinline__ uint32_t ld_le32(const uint8_t* p) {
-  return static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8) |
-         (static_cast<uint32_t>(p[2]) << 16) | (static_cast<uint32_t>(p[3]) << 24);
-}
-
-// GetVarint64Ptr / GetVarint32Ptr (util/coding.cc): bytes consumed, 0 on
-// failure (runs past `limit` or longer than the type allows).
-__device__ __forceinline__ uint32_t get_varint(const uint8_t* p, const uint8_t* limit, uint32_t max_shift,
-                               uint64_t* v) {
-  uint64_t result = 0;
-  uint32_t i = 0;
-  for (uint32_t shift = 0; shift <= max_shift && p + i < limit; shift += 7, ++i) {
-    const uint64_t b = p[i];
-    if (b & 128) {
-      result |= (b & 127) << shift;
-    } else {
-      *v = result | (b << shift);
-      return i + 1;
-    }
-  }
-  return 0;
-}
-
 // BlockHandle::DecodeFrom over [p, limit): true and (off, size) on success.
 __device__ __forceinline__ bool decode_handle(const uint8_t* p, const uint8_t* limit, uint64_t* off,
                               uint64_t* size, const uint8_t** next) {
-  const uint32_t n1 = get_varint(p, limit, 63, off);
+  const uint32_t n1 = get_varint(p, limit, off);
   if (n1 == 0) return false;
-  const uint32_t n2 = get_varint(p + n1, limit, 63, size);
+  const uint32_t n2 = get_varint(p + n1, limit, size);
   if (n2 == 0) return false;
   if (next) *next = p + n1 + n2;
   return true;
@@ -149,26 +125,6 @@ __device__ __forceinline__ uint8_t read_status(bool crc_ok, uint8_t type) {
   if (type == 1 || type == 2) return LVKV_BLOCK_COMPRESSED;  // no codec as built
   if (type > 2) return LVKV_BLOCK_BAD_TYPE;
   return LVKV_BLOCK_OK;
-}
-
-// DecodeEntry (table/block.cc:55-75): pointer to the key delta or nullptr.
-__device__ __forceinline__ const uint8_t* decode_entry(const uint8_t* p, const uint8_t* limit, uint32_t* shared,
-                                       uint32_t* non_shared, uint32_t* value_len) {
-  if (limit - p < 3) return nullptr;
-  uint64_t v;
-  uint32_t n;
-  if ((n = get_varint(p, limit, 28, &v)) == 0) return nullptr;
-  *shared = static_cast<uint32_t>(v);
-  p += n;
-  if ((n = get_varint(p, limit, 28, &v)) == 0) return nullptr;
-  *non_shared = static_cast<uint32_t>(v);
-  p += n;
-  if ((n = get_varint(p, limit, 28, &v)) == 0) return nullptr;
-  *value_len = static_cast<uint32_t>(v);
-  p += n;
-  if (static_cast<uint64_t>(limit - p) < static_cast<uint64_t>(*non_shared) + *value_len)
-    return nullptr;
-  return p;
 }
 
 // Everything the table's workgroup shares, in LDS.

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "lvkv_launch.h"
+#include "lvkv_lds_bytes.h"
 #include "lvkv_snappy.h"
 #include "lvkv_zstd_tables.h"
 
@@ -35,44 +36,14 @@ enum : uint32_t {
   kFTrailing, kFSkippable, kFEmpty
 };
 
-__device__ __forceinline__ uint32_t ld32(const uint8_t* b, uint32_t p) {
-  const uint32_t* d = reinterpret_cast<const uint32_t*>(b + (p & ~3u));
-  return __builtin_amdgcn_alignbyte(d[1], d[0], p & 3u);
-}
-__device__ __forceinline__ uint64_t ld64(const uint8_t* b, uint32_t p) {
-  const uint32_t* d = reinterpret_cast<const uint32_t*>(b + (p & ~3u));
-  const uint32_t s = p & 3u;
-  const uint32_t lo = __builtin_amdgcn_alignbyte(d[1], d[0], s);
-  const uint32_t hi = __builtin_amdgcn_alignbyte(d[2], d[1], s);
-  return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
-// Wave-uniform reads. The parser's values are the same in every lane; an
-// LDS or global load still lands in a VGPR, and everything computed from it
-// would run as divergent code (exec masks, VALU), so the loads that steer
-// control flow go through v_readfirstlane into SGPRs.
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+// Wave-uniform reads (lvkv_lds_bytes.h's uni): the parser's values are the
+// same in every lane.
 __device__ __forceinline__ uint32_t ldb(const uint8_t* b, uint32_t p) { return uni(b[p]); }
 __device__ __forceinline__ uint32_t ld32u(const uint8_t* b, uint32_t p) { return uni(ld32(b, p)); }
 __device__ __forceinline__ uint64_t ld64u(const uint8_t* b, uint32_t p) {
   const uint64_t v = ld64(b, p);
   return (static_cast<uint64_t>(uni(static_cast<uint32_t>(v >> 32))) << 32) |
          uni(static_cast<uint32_t>(v));
-}
-
-// Global -> LDS (4-aligned), as the Snappy kernels stage (aligned dword loads
-// at any source alignment, nothing read past the block's last dword).
-__device__ __forceinline__ void stage(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t pad,
-                                      uint32_t lane) {
-  const uint32_t mis = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(src)) & 3u;
-  const uint32_t* s = reinterpret_cast<const uint32_t*>(src - mis);
-  const uint32_t nd = (n + 3u) >> 2;
-  for (uint32_t i = lane; i < nd; i += 64) {
-    const uint32_t lo = s[i];
-    const uint32_t hi = (mis != 0 && 4u * (i + 1u) < mis + n) ? s[i + 1] : 0u;
-    reinterpret_cast<uint32_t*>(dst)[i] = __builtin_amdgcn_alignbyte(hi, lo, mis);
-  }
-  for (uint32_t i = n + lane; i < n + pad; i += 64) dst[i] = 0;
 }
 
 // ---- backward bitstreams (RFC 8878 §4.1.1.1) ------------------------------

@@ -39,6 +39,7 @@
 #include <stdint.h>
 
 #include "lvkv_launch.h"
+#include "lvkv_lds_bytes.h"
 #include "lvkv_zstd.h"
 
 namespace lvkv {
@@ -47,7 +48,6 @@ namespace {
 constexpr uint32_t kTags = 1024;  // window-scratch slots (u32)
 constexpr uint32_t kLitStage = 32;  // the literals' offset in the frame slot (past the header)
 
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 // Every lane's LDS operations so far are ordered before what follows. The
 // workgroup is one wave, and one wave's LDS instructions execute in issue
 // order (the counted lgkmcnt waits rest on it), so a later LDS access of any
@@ -81,21 +81,10 @@ __device__ __forceinline__ T wave_max(T v) {
 
 __host__ __device__ __forceinline__ uint32_t hibit(uint32_t v) { return 31u - __builtin_clz(v); }
 
-__device__ __forceinline__ uint32_t ld32(const uint8_t* b, uint32_t p) {
-  const uint32_t* d = reinterpret_cast<const uint32_t*>(b + (p & ~3u));
-  return __builtin_amdgcn_alignbyte(d[1], d[0], p & 3u);
-}
-__device__ __forceinline__ uint64_t ld64(const uint8_t* b, uint32_t p) {
-  const uint32_t* d = reinterpret_cast<const uint32_t*>(b + (p & ~3u));
-  const uint32_t s = p & 3u;
-  const uint32_t lo = __builtin_amdgcn_alignbyte(d[1], d[0], s);
-  const uint32_t hi = __builtin_amdgcn_alignbyte(d[2], d[1], s);
-  return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
 // The block's copy: dst[0, n) = src[0, n), then 16 zero bytes (up to the
 // dword). dst is dword-aligned; src is read in aligned dwords that hold at
-// least one byte of the block, and no byte past the block reaches dst.
+// least one byte of the block, and no byte past the block reaches dst
+// (lvkv_lds_bytes.h's stage, with the last dword masked instead of overwritten).
 __device__ __forceinline__ void stage(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
   const uint32_t mis = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(src)) & 3u;
   const uint32_t* s = reinterpret_cast<const uint32_t*>(src - mis);

@@ -187,6 +187,23 @@ def test_sizing_functions_are_monotone(lvkv):
             assert f == sorted(f), (arg, f)
 
 
+def test_sizing_functions_answer_as_recorded(lvkv):
+    """tests/golden/scratch_sizes.json (gen_scratch_sizes.py): every value of
+    the write path's seven sizing functions over a grid that crosses their
+    branches. Callers allocate by these; no layout change may move one."""
+    calls = json.loads((GOLDEN / "scratch_sizes.json").read_text())["calls"]
+    assert sorted(calls) == [
+        "lvkv_sst_build_blocks_raw_bound", "lvkv_sst_build_blocks_scratch_bytes",
+        "lvkv_sst_table_file_bound", "lvkv_sst_write_scratch_bytes",
+        "lvkv_sst_write_scratch_bytes_v2", "lvkv_sst_write_table_scratch_bytes",
+        "lvkv_zstd_compress_big_scratch_bytes"]
+    assert sum(len(rows) for rows in calls.values()) > 700
+    for fn, rows in calls.items():
+        f = getattr(lvkv.lib, fn)
+        for *args, want in rows:
+            assert f(*args) == want, (fn, args)
+
+
 def _cases():
     """(name, blocks, key_format, bits) of every table the GPU tests build."""
     for name in ["table"] + FIXTURES:
@@ -301,12 +318,15 @@ def test_bench_blocks_internal_keys(lvkv, gpu, compression):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("compression", [0, 1])
-def test_many_small_blocks_share_filters(lvkv, gpu, compression):
-    """4,101 blocks: five passes of the slot scan, two of the writer's layout,
-    five of the finisher's; some fifty blocks a filter."""
-    raws = _tiny_blocks(4101)
+@pytest.mark.parametrize("nblocks", [1024, 1025, 4101])
+def test_many_small_blocks_share_filters(lvkv, gpu, compression, nblocks):
+    """The scans that carry a total from one pass of 1,024 blocks to the next
+    (the slot scan, the finisher's three), at exactly one pass, at one block
+    past it, and at 4,101 blocks: five passes of those, two of the writer's
+    layout; some fifty blocks a filter."""
+    raws = _tiny_blocks(nblocks)
     t = _model(raws, 0, 10, compression)
-    assert t.report["nfilters"] < 4101 // 40
+    assert t.report["nfilters"] < nblocks // 40
     _expect(_write(lvkv, gpu, raws, key_format=0, bits=10, compression=compression), t)
 
 
