@@ -47,7 +47,7 @@ HIP_SOURCES = ["crc32c_kernel.hip", "crc32c_uniform.hip", "crc32c_compact.hip",
 ENGINE_KERNELS = "lvkv_engine_kernels.hip"
 HEADERS = ["lvkv_kernel_args.h", "lvkv_tables.h", "crc32c_device_common.h",
            "crc32c_uniform_common.h", "crc32c_compact_common.h", "crc32c_burst.h",
-           "crc32c_ragged_body.h", "lvkv_log_events.h", "lvkv_zstd_tables.h", "lvkv_launch.h",
+           "crc32c_ragged_body.h", "crc32c_modes.h", "lvkv_log_events.h", "lvkv_zstd_tables.h", "lvkv_launch.h",
            "lvkv_block_scan.h", "lvkv_scratch.h", "lvkv_table_format.h", "lvkv_lds_bytes.h"]
 
 

@@ -17,6 +17,7 @@
 
 #include "crc32c_device_common.h"
 #include "crc32c_compact_common.h"
+#include "crc32c_modes.h"
 #include "crc32c_uniform_common.h"
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
@@ -211,29 +212,26 @@ __global__ void __launch_bounds__(64 * W, OCC) crc32c_compact_kernel(UniformArgs
 }
 
 // ---------------------------------------------------------------------------
-// Long blocks of the general batch (covered length > kLongBytes), one
+// Long blocks of the general batch (covered length > long_split), one
 // workgroup per block instead of one wave: the bytes up to the last 4-byte
 // boundary are cut at absolute 4-byte-aligned points into kLongSeg segments;
 // wave w checksums segments w, w + 16, ... (segment 0 from init ^ ~0, the
 // others from register 0), shifts each register to that boundary with Z_n =
 // the product of the Z_{2^j} byte tables (zpow, HBM), and xors it into its
 // accumulator. Wave 0 combines the 16 accumulators, feeds the 0-3 tail bytes
-// through the byte table (Z_1) and stores in the batch's mode (compute, SST
-// verify, SST fill). The main batch kernel skips exactly these blocks
-// (KernelArgs::long_split). Bytes read per block: its covered length once.
+// through the byte table (Z_1) and stores in the batch's mode (crc32c_modes.h:
+// compute, SST verify, SST fill). The main batch kernel skips exactly these
+// blocks (KernelArgs::long_split). Bytes read per block: its covered length once.
 
 namespace {
 
 constexpr int kLongWaves = 16;
 
-__device__ __forceinline__ uint32_t ld_le32_g(const uint8_t* t) {
-  return static_cast<uint32_t>(t[0]) | (static_cast<uint32_t>(t[1]) << 8) |
-         (static_cast<uint32_t>(t[2]) << 16) | (static_cast<uint32_t>(t[3]) << 24);
-}
-
 }  // namespace
 
-__global__ void __launch_bounds__(1024, 1)
+// 8 waves per SIMD: two of these workgroups share a CU (the LDS allows two),
+// so at most 64 VGPRs.
+__global__ void __launch_bounds__(1024, 8)
     crc32c_long_kernel(KernelArgs a, const uint32_t* zpow, const uint32_t* lane_cols) {
   constexpr int W = kLongWaves;
   // LDS: the compact image, one accumulator per wave, the slice's long-block
@@ -244,9 +242,6 @@ __global__ void __launch_bounds__(1024, 1)
   const uint32_t lane = lane_id();
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t n = a.count != nullptr ? min(a.nblocks, sload_u32(a.count, 0)) : a.nblocks;
-  const uint64_t base = reinterpret_cast<uint64_t>(a.base);
-  const bool sst = a.mode == kModeSstVerify || a.mode == kModeSstFill;
-  const uint32_t extra = sst ? 1u : 0u;
   bool built = false;
   const LaneKeys keys = lane_keys(lane);
   const uint32_t lane_base = (lane >> 5) * 256u + 128u + (lane & 31u) * 4u;
@@ -258,42 +253,30 @@ __global__ void __launch_bounds__(1024, 1)
     if (tid == 0) lds[kCount] = 0;
     __syncthreads();
     const uint32_t i = slice + tid;
-    if (i < last && a.lengths[i] + extra > kLongBytes) lds[kList + atomicAdd(&lds[kCount], 1u)] = i;
+    if (i < last && mode_covered_len<false>(a, i) > a.long_split)
+      lds[kList + atomicAdd(&lds[kCount], 1u)] = i;
     __syncthreads();
     const uint32_t cnt = __builtin_amdgcn_readfirstlane(lds[kCount]);
     for (uint32_t li = 0; li < cnt; ++li) {
       const uint32_t b = __builtin_amdgcn_readfirstlane(lds[kList + li]);
-      const uint64_t off = sload_u64(a.offsets, b);
-      const uint64_t len = static_cast<uint64_t>(sload_u32(a.lengths, b)) + extra;
-      const uint32_t init = sst ? 0u : (a.inits != nullptr ? sload_u32(a.inits, b) : a.init);
+      const Covered c = mode_covered<false>(a, b, false);
       if (!built) {  // the compact LDS image, once per workgroup
         build_compact_image<kLongWaves>(lds, zpow, lane_cols, tid, wave, lane);
         built = true;
       }
-      const uint64_t start = base + off, end = start + len;
-      const uint32_t crc =
-          workgroup_crc<kLongWaves>(lds, lds + kAcc, start, end, init, keys, tid, wave, lane, lane_base, zpow);
-      if (tid == 0) {
-        if (a.mode == kModeSstFill) {
-          uint8_t* dst = reinterpret_cast<uint8_t*>(end);
-          const uint32_t mcrc = crc_mask(crc);
-          for (int k = 0; k < 4; ++k) dst[k] = static_cast<uint8_t>(mcrc >> (8 * k));
-          if (a.out_crc != nullptr) a.out_crc[b] = crc;
-        } else if (a.mode == kModeSstVerify) {
-          a.out_crc[b] = crc;
-          if (a.out_status != nullptr)
-            a.out_status[b] = crc != crc_unmask(ld_le32_g(reinterpret_cast<const uint8_t*>(end)));
-        } else {
-          a.out_crc[b] = a.mask ? crc_mask(crc) : crc;
-        }
-      }
+      const uint32_t crc = workgroup_crc<kLongWaves>(lds, lds + kAcc, c.ptr, c.ptr + c.len, c.init,
+                                                     keys, tid, wave, lane, lane_base, zpow);
+      if (tid == 0) mode_store<false>(a, b, c.ptr, c.len, c.expected, crc);
     }
     __syncthreads();
   }
 }
 
+// The scan reads a.lengths, which a WAL batch does not have, and
+// kModeSstTable is the ragged walk's alone (launch_crc32c_general).
 hipError_t launch_crc32c_long(const KernelArgs& args, const uint32_t* zpow,
                               const uint32_t* lane_cols, int num_groups, hipStream_t stream) {
+  if (mode_is_log(args.mode) || args.mode == kModeSstTable) return hipErrorInvalidValue;
   hipLaunchKernelGGL(crc32c_long_kernel, dim3(num_groups), dim3(1024), 0, stream, args, zpow,
                      lane_cols);
   return hipGetLastError();

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "crc32c_device_common.h"
+#include "crc32c_modes.h"
 #include "crc32c_uniform_common.h"
 #include "lvkv_kernel_args.h"
 
@@ -313,16 +314,6 @@ __device__ __forceinline__ uint32_t apply_lane_cols(uint32_t colv, uint32_t v, u
                                                     uint32_t lane) {
   const bool on = (lane >> 5) == h && ((v >> (lane & 31u)) & 1u);
   return wave_xor_dpp(on ? colv : 0u);
-}
-
-// Bitwise register update over the n (< 4) little-endian bytes of `bytes`.
-__device__ __forceinline__ uint32_t crc_bytes_bitwise(uint32_t reg, uint32_t bytes, uint32_t n) {
-  for (uint32_t i = 0; i < n; ++i) {
-    reg ^= (bytes >> (8u * i)) & 0xffu;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) reg = (reg >> 1) ^ (kCastagnoliReflected & (0u - (reg & 1u)));
-  }
-  return reg;
 }
 
 // Smallest segment (log2, 2^10 .. 2^15 bytes) that gives each of GW waves at

@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "crc32c_device_common.h"
+#include "crc32c_modes.h"
 #include "lvkv_kernel_args.h"
 #include "lvkv_launch.h"
 
@@ -171,47 +172,20 @@ __device__ __forceinline__ Geo make_geo(const KernelArgs& a, uint32_t b) {
     return g;
   }
   if (b >= a.nblocks) return null_geo();
-  const uint64_t base = reinterpret_cast<uint64_t>(a.base);
-  uint64_t off;
-  uint32_t len, init = a.init, expected = 0;
-  if (a.mode == kModeLogVerify || a.mode == kModeLogFill) {
-    // Header [masked crc u32][len u16][type u8]; CRC covers type + payload
-    // (db/log_reader.cc:217-221, 243-247).
-    const uint64_t hoff = sload_u64(a.offsets, b);
-    const uint64_t hdr = base + hoff;
-    const uint32_t len_type = sload_le(hdr + 4, 3);
-    if (a.mode == kModeLogVerify) expected = crc_unmask(sload_le(hdr, 4));
-    off = hoff + 6;
-    len = 1u + (len_type & 0xffffu);
-    init = 0;
-  } else if (a.offsets != nullptr) {
-    off = sload_u64(a.offsets, b);
-    len = sload_u32(a.lengths, b);
-    if (a.inits != nullptr) init = sload_u32(a.inits, b);
-  } else {
-    off = static_cast<uint64_t>(b) * a.stride;
-    len = a.length;
-  }
-  if (a.mode == kModeSstVerify || a.mode == kModeSstFill) {
-    // Block contents n bytes + type byte are covered; the masked CRC follows
-    // (table/format.cc:92-94, table/table_builder.cc:199-203).
-    len += 1;
-    init = 0;
-    if (a.mode == kModeSstVerify) expected = crc_unmask(sload_le(base + off + len, 4));
-  }
-
-  if (a.long_split && len > kLongBytes) {  // crc32c_long_kernel's block
+  const Covered c = mode_covered<false>(a, b, false);
+  const uint32_t len = c.len;
+  if (a.long_split && len > a.long_split) {  // crc32c_long_kernel's block
     Geo g = null_geo();
     g.tiny = 2;
     return g;
   }
   Geo g;
-  const uint64_t ptr = base + off;
+  const uint64_t ptr = c.ptr;
   g.ptr_lo = static_cast<uint32_t>(ptr);
   g.ptr_hi = static_cast<uint32_t>(ptr >> 32);
   g.len = len;
-  g.s0 = init ^ 0xffffffffu;
-  g.expected = expected;
+  g.s0 = c.init ^ 0xffffffffu;
+  g.expected = c.expected;
   if (len < 4) {
     g.b4_lo = 0;
     g.b4_hi = 0;
@@ -338,42 +312,17 @@ __device__ __forceinline__ void prep_chunk(uint32_t (&buf)[kRowsPerChunk + 1],
   }
 }
 
-__device__ __forceinline__ uint32_t tiny_crc(const Geo& g) {
-  uint32_t reg = g.s0;
-  if (g.len > 0) {
-    const uint32_t bytes = sload_le(g.ptr(), g.len);
-    for (uint32_t i = 0; i < g.len; ++i) {
-      reg ^= (bytes >> (8u * i)) & 0xffu;
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        reg = (reg >> 1) ^ (kCastagnoliReflected & (0u - (reg & 1u)));
-    }
-  }
-  return reg ^ 0xffffffffu;
-}
-
+// The uniform-aligned variant is compute mode by construction; every other
+// batch stores in its mode.
 template <int V>
 __device__ __forceinline__ void store_result(const KernelArgs& a,
                                              const Item& it, uint32_t crc) {
-  if (!(V & kUniformAligned) && it.g.tiny == 2) return;
-  if (lane_id() == 0) {
-    if ((V & kUniformAligned) || a.mode == kModeCompute) {
-      a.out_crc[it.block] = a.mask ? crc_mask(crc) : crc;
-    } else if (a.mode == kModeSstFill || a.mode == kModeLogFill) {
-      // The stored form (Mask, little-endian) into the trailer / header hole:
-      // trailer bytes 1..4 follow the covered n+1 bytes; the header CRC sits
-      // 6 bytes before the covered type byte.
-      const uint64_t ptr = (static_cast<uint64_t>(it.g.ptr_hi) << 32) | it.g.ptr_lo;
-      uint8_t* dst = reinterpret_cast<uint8_t*>(a.mode == kModeSstFill ? ptr + it.g.len : ptr - 6);
-      const uint32_t m = crc_mask(crc);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) dst[k] = static_cast<uint8_t>(m >> (8 * k));
-      if (a.out_crc != nullptr) a.out_crc[it.block] = crc;
-    } else {
-      a.out_crc[it.block] = crc;
-      if (a.out_status != nullptr) a.out_status[it.block] = (crc != it.g.expected) ? 1 : 0;
-    }
+  if (V & kUniformAligned) {
+    if (lane_id() == 0) a.out_crc[it.block] = a.mask ? crc_mask(crc) : crc;
+    return;
   }
+  if (it.g.tiny == 2) return;
+  mode_store<false>(a, it.block, it.g.ptr(), it.g.len, it.g.expected, crc);
 }
 
 template <int V>
@@ -459,10 +408,12 @@ __device__ __forceinline__ void consume2(
   } else {
     if (fin_a)
       store_result<V>(a, ia, (!(V & kUniformAligned) && ia.g.tiny)
-                                 ? tiny_crc(ia.g) : finish_value<V>(lds, sa, lane_base));
+                                 ? crc_tiny(ia.g.ptr(), ia.g.len, ia.g.s0)
+                                 : finish_value<V>(lds, sa, lane_base));
     if (fin_b)
       store_result<V>(a, ib, (!(V & kUniformAligned) && ib.g.tiny)
-                                 ? tiny_crc(ib.g) : finish_value<V>(lds, sb, lane_base));
+                                 ? crc_tiny(ib.g.ptr(), ib.g.len, ib.g.s0)
+                                 : finish_value<V>(lds, sb, lane_base));
   }
 }
 

@@ -8,6 +8,7 @@
 
 #include "crc32c_compact_common.h"
 #include "crc32c_device_common.h"
+#include "crc32c_modes.h"
 #include "crc32c_ragged_body.h"
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
@@ -66,17 +67,16 @@ hipError_t launch_crc32c_ragged(const KernelArgs& a, const uint32_t* zpow,
 
 // General-layout batch (a.offsets set, a.row_tab = the device tables) on
 // `cus` CUs; a.nblocks is the launch's capacity when a.count is set. Blocks
-// over kLongBytes are included when a.long_split is set.
+// over a.long_split bytes are included when it is set.
 hipError_t launch_crc32c_general(const KernelArgs& a, int cus, hipStream_t stream) {
   const uint32_t n = a.nblocks;
   if (n == 0) return hipSuccess;
-  // (kModeSstTable exists in this kernel only)
-  const bool log = a.mode == kModeLogVerify || a.mode == kModeLogFill;
+  const bool log = mode_is_log(a.mode);
   // a.general_cfg: a ragged cfg (>= 0) or -1 for crc32c_kernel.hip's
   // persistent kernel; a.log_cfg: the shape for WAL records (the device
   // context's choices, lvkv_capi.cpp)
   int cfg = log && a.general_cfg >= 0 ? a.log_cfg : a.general_cfg;
-  if (a.mode == kModeSstTable && cfg < 0) cfg = 0;
+  if (a.mode == kModeSstTable && cfg < 0) cfg = 0;  // the ragged walk alone serves it
   if (cfg < 0) {  // the persistent kernel and, for long blocks, a second launch
     KernelArgs b = a;
     if (log) b.long_split = 0;  // crc32c_long_kernel has no WAL modes

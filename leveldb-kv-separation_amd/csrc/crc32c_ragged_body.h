@@ -23,7 +23,7 @@
 // Work map: G contiguous runs of equal length. A run is walked in rounds of
 // W * NCH blocks: wave w, chain c takes block c * W + w of the round. Each
 // chain's block is read in chunks of R rows, all chains' loads in flight
-// together, chains walked interleaved. Blocks over 64 KiB (long_split) are
+// together, chains walked interleaved. Blocks over long_split bytes are
 // walked at the end of the run by the whole workgroup, blocks under 4 bytes
 // bitwise by lane 0.
 #ifndef LVKV_CRC32C_RAGGED_BODY_H_
@@ -34,6 +34,7 @@
 
 #include "crc32c_compact_common.h"
 #include "crc32c_device_common.h"
+#include "crc32c_modes.h"
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
 
@@ -83,185 +84,56 @@ struct RagBlock {
   }
 };
 
-// Descriptor b. Written by an earlier launch: through the scalar cache.
-// Written by workgroups of this same launch (a.fresh_desc, the fused SST
-// verify): vector loads after the caller's acquire, never a scalar-cache line
-// that could predate the write.
-__device__ __forceinline__ uint64_t desc_u64(const KernelArgs& a, uint32_t b) {
-  if (!a.fresh_desc) return sload_u64(a.offsets, b);
-  const uint64_t v = __hip_atomic_load(a.offsets + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-  return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-__device__ __forceinline__ uint32_t desc_u32(const KernelArgs& a, uint32_t b) {
-  if (!a.fresh_desc) return sload_u32(a.lengths, b);
-  return __builtin_amdgcn_readfirstlane(
-      __hip_atomic_load(a.lengths + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
-// Block b's covered range and verdict inputs by mode (crc32c_kernel.hip
-// make_geo: log headers, SST trailers, per-block inits).
-// With `defer`, an SST mode's stored trailer is not loaded here: the walk
-// loads it with a vector load when the block's round starts (RagRound::adopt)
-// and reads it at the store, so no scalar load is outstanding while the walk
-// waits on its LDS reads (one lgkmcnt counts both).
-__device__ __forceinline__ RagBlock rag_block(const KernelArgs& a, uint32_t b, bool live,
-                                              bool defer = false) {
+// No block: an idle chain, or an entry the caller's source leaves out.
+__device__ __forceinline__ RagBlock rag_none() {
   RagBlock g;
   g.ptr_lo = g.ptr_hi = g.len = g.s0 = g.expected = 0;
   g.kind = kRagNone;
-  if (!live) return g;
-  const uint64_t base = reinterpret_cast<uint64_t>(a.base);
-  uint64_t off;
-  uint32_t len, init = a.init, expected = 0;
-  if (a.mode == kModeLogVerify || a.mode == kModeLogFill || a.mode == kModeLogStaged) {
-    // [masked crc u32][len u16][type u8]; the CRC covers type + payload
-    // (db/log_reader.cc:217-221, 243-247).
-    const uint64_t hoff = desc_u64(a, b);
-    const uint32_t len_type = sload_le(base + hoff + 4, 3);
-    if (a.mode != kModeLogFill) expected = crc_unmask(sload_le(base + hoff, 4));
-    off = hoff + 6;
-    len = 1u + (len_type & 0xffffu);
-    init = 0;
-  } else {
-    if (a.offsets == nullptr) {  // uniform layout: block b at base + b * stride
-      off = static_cast<uint64_t>(b) * a.stride;
-      len = a.length;
-    } else {
-      off = desc_u64(a, b);
-      len = desc_u32(a, b);
-    }
-    if (a.inits != nullptr) init = sload_u32(a.inits, b);
-  }
-  if (a.mode == kModeSstVerify || a.mode == kModeSstFill || a.mode == kModeSstTable) {
-    // contents n bytes + type byte; the masked CRC follows
-    // (table/format.cc:92-94, table/table_builder.cc:199-203)
-    len += 1;
-    init = 0;
-    if (a.mode != kModeSstFill && !defer) expected = crc_unmask(sload_le(base + off + len, 4));
-  }
-  const uint64_t ptr = base + off;
-  g.ptr_lo = static_cast<uint32_t>(ptr);
-  g.ptr_hi = static_cast<uint32_t>(ptr >> 32);
-  g.len = len;
-  g.s0 = init ^ 0xffffffffu;
-  g.expected = expected;
-  if (a.long_split && len > a.long_split) {
-    g.kind = kRagSkip;
-    return g;
-  }
-  if (len < 4) {
-    g.kind = kRagTiny;
-    return g;
-  }
-  g.kind = kRagRows;
   return g;
 }
 
-__device__ __forceinline__ uint32_t rag_tiny(const RagBlock& g) {
-  uint32_t reg = g.s0;
-  if (g.len > 0) {
-    const uint32_t bytes = sload_le(g.ptr(), g.len);
-    for (uint32_t i = 0; i < g.len; ++i) {
-      reg ^= (bytes >> (8u * i)) & 0xffu;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) reg = (reg >> 1) ^ (kCastagnoliReflected & (0u - (reg & 1u)));
-    }
-  }
-  return reg ^ 0xffffffffu;
+// How a block of `len` covered bytes is walked: by the whole workgroup at the
+// end of the run (over long_split), bitwise by lane 0, or in rows.
+__device__ __forceinline__ uint32_t rag_kind(uint32_t len, uint32_t long_split) {
+  return long_split && len > long_split ? kRagSkip : len < 4 ? kRagTiny : kRagRows;
 }
 
-// A value written by this launch's other workgroups (a.fresh_desc) or by an
-// earlier launch: agent-scope atomic load or a plain one.
-template <typename T>
-__device__ __forceinline__ T fresh_ld(const KernelArgs& a, const T* p) {
-  return a.fresh_desc ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-}
-
-// Table of entry e in kModeSstTable: the last report whose first <= e.
-__device__ __forceinline__ uint32_t sst_table_of(const KernelArgs& a,
-                                                 const lvkv_sst_report* reports, uint32_t ntables,
-                                                 uint32_t e) {
-  uint32_t lo = 0, hi = ntables;  // answer in [lo, hi)
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (fresh_ld(a, &reports[mid].first) <= e) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// Lane 0 stores block b's result in the batch's mode.
-__device__ __forceinline__ void rag_store(const KernelArgs& a, uint32_t b, const RagBlock& g,
-                                          uint32_t crc) {
-  if (lane_id() != 0) return;
-  if (a.mode == kModeSstTable) {
-    // ReadBlock's order (format.cc:92-97, :104-158): the index parse status
-    // first, then the checksum, then the type byte
-    uint8_t st = fresh_ld(a, a.out_status + b);
-    a.out_crc[b] = st == LVKV_BLOCK_OK ? crc : 0u;  // no CRC of an unreadable block
-    if (st == LVKV_BLOCK_OK) {
-      const uint8_t type = *reinterpret_cast<const uint8_t*>(g.ptr() + g.len - 1);
-      if (crc != g.expected)
-        st = LVKV_BLOCK_CHECKSUM;
-      else if (type == 1 || type == 2)  // snappy / zstd: absent in the as-built
-        st = LVKV_BLOCK_COMPRESSED;     // reference (port_stdcxx.h:108-118)
-      else if (type > 2)
-        st = LVKV_BLOCK_BAD_TYPE;
-      if (st != LVKV_BLOCK_OK) a.out_status[b] = st;
-    }
-    if (st != LVKV_BLOCK_OK) {
-      lvkv_sst_report* reps = static_cast<lvkv_sst_report*>(a.sst_reports);
-      lvkv_sst_report* r = reps + sst_table_of(a, reps, a.sst_ntables, b);
-      atomicAdd(&r->nbad, 1u);
-      atomicMin(&r->first_bad, b - fresh_ld(a, &r->first));
-    }
-  } else if (a.mode == kModeCompute) {
-    a.out_crc[b] = a.mask ? crc_mask(crc) : crc;
-  } else if (a.mode == kModeSstFill || a.mode == kModeLogFill) {
-    // the stored form (Mask, little-endian) into the trailer / header hole
-    uint8_t* dst = reinterpret_cast<uint8_t*>(a.mode == kModeSstFill ? g.ptr() + g.len
-                                                                     : g.ptr() - 6);
-    const uint32_t m = crc_mask(crc);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dst[k] = static_cast<uint8_t>(m >> (8 * k));
-    if (a.out_crc != nullptr) a.out_crc[b] = crc;
-  } else {
-    a.out_crc[b] = crc;
-    if (a.out_status != nullptr) a.out_status[b] = crc != g.expected ? 1 : 0;
-    if (a.mode == kModeLogStaged && crc != g.expected) {
-      // the block's first mismatch (its records are staged in file order)
-      const uint64_t hoff = g.ptr() - 6u - reinterpret_cast<uint64_t>(a.base);
-      atomicMin(a.log_first_bad + (hoff >> 15), b);
-    }
-  }
+// Block b of the batch in its mode (crc32c_modes.h). With `defer`, an SST
+// mode's stored trailer is not loaded here: the walk loads it when the
+// block's round starts (RagRound::adopt) and reads it at the store.
+__device__ __forceinline__ RagBlock rag_block(const KernelArgs& a, uint32_t b, bool live,
+                                              bool defer = false) {
+  RagBlock g = rag_none();
+  if (!live) return g;
+  const Covered c = mode_covered<true>(a, b, defer);
+  g.ptr_lo = static_cast<uint32_t>(c.ptr);
+  g.ptr_hi = static_cast<uint32_t>(c.ptr >> 32);
+  g.len = c.len;
+  g.s0 = c.init ^ 0xffffffffu;
+  g.expected = c.expected;
+  g.kind = rag_kind(c.len, a.long_split);
+  return g;
 }
 
 // Where a walk's blocks come from and where its results go: the batch's
-// descriptor arrays and rag_store (ArgsSrc), or a caller's own list (the
+// descriptor arrays and mode_store (ArgsSrc), or a caller's own list (the
 // whole-SSTable verify's entries decoded into LDS, lvkv_sst_table.hip).
 struct ArgsSrc {
   // the stored CRC follows the covered bytes (SST verify modes): loaded by
   // the walk (RagRound::adopt), not by block()
   __device__ __forceinline__ bool trailer(const KernelArgs& a) const {
-    return a.mode == kModeSstVerify || a.mode == kModeSstTable;
+    return mode_has_trailer(a.mode);
   }
   __device__ __forceinline__ RagBlock block(const KernelArgs& a, uint32_t b, bool live) const {
     return rag_block(a, b, live, trailer(a));
   }
   __device__ __forceinline__ void store(const KernelArgs& a, uint32_t b, const RagBlock& g,
                                         uint32_t crc) const {
-    rag_store(a, b, g, crc);
+    mode_store<true>(a, b, g.ptr(), g.len, g.expected, crc);
   }
-  // covered length of block b, as rag_block computes it (the long-block scan)
+  // covered length of block b (the long-block scan)
   __device__ __forceinline__ uint32_t covered(const KernelArgs& a, uint32_t b) const {
-    const bool sst = a.mode == kModeSstVerify || a.mode == kModeSstFill || a.mode == kModeSstTable;
-    const bool log = a.mode == kModeLogVerify || a.mode == kModeLogFill || a.mode == kModeLogStaged;
-    if (log) {
-      const uint8_t* h = a.base + fresh_ld(a, a.offsets + b);
-      return 1u + (static_cast<uint32_t>(h[4]) | (static_cast<uint32_t>(h[5]) << 8));
-    }
-    return (a.offsets == nullptr ? a.length : fresh_ld(a, a.lengths + b)) + (sst ? 1u : 0u);
+    return mode_covered_len<true>(a, b);
   }
 };
 
@@ -362,7 +234,7 @@ struct RagLds {
                             kCount = kList + 64 * W, kDwords = kCount + 1;
 };
 
-// Blocks over kLongBytes in the run [start, start + n) (rare): the whole
+// Blocks over long_split in the run [start, start + n) (rare): the whole
 // workgroup walks each one, 16 KiB segments over the waves (workgroup_crc),
 // instead of a second kernel launch per batch. The run's lengths are scanned
 // 64 * W at a time only when a wave met one (lds[kFlag], set by the walk).
@@ -418,19 +290,9 @@ __device__ __forceinline__ void ragged_run(const KernelArgs& a, const uint32_t* 
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = lane_id();
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  uint32_t start, n;
-  if (a.run_base != nullptr) {  // runs of whole units (bytes balanced)
-    const uint32_t U = a.run_units;
-    const uint32_t u0 = static_cast<uint32_t>(static_cast<uint64_t>(grp) * U / G);
-    const uint32_t u1 = static_cast<uint32_t>(static_cast<uint64_t>(grp + 1) * U / G);
-    start = min(total, sload_u32(a.run_base, u0));
-    const uint32_t end = u1 < U ? min(total, sload_u32(a.run_base, u1)) : total;
-    n = end > start ? end - start : 0u;
-  } else {
-    const uint32_t per = total / G, extra = total % G;
-    n = per + (grp < extra ? 1u : 0u);
-    start = grp * per + min(grp, extra);
-  }
+  const uint32_t per = total / G, extra = total % G;
+  const uint32_t n = per + (grp < extra ? 1u : 0u);
+  const uint32_t start = grp * per + min(grp, extra);
   if (n == 0) return;  // the whole workgroup: no barrier is left waiting
 
   // 1. table loads, round 0's first chunk in flight, the LDS image, barrier
@@ -531,7 +393,8 @@ __device__ __forceinline__ void ragged_run(const KernelArgs& a, const uint32_t* 
       for (int c = 0; c < NCH; ++c) {
         if (rd.g[c].kind == kRagTiny) {
           if (src.trailer(a)) rd.g[c].expected = rd.expected(c);
-          src.store(a, rd.blk[c], rd.g[c], rag_tiny(rd.g[c]));
+          src.store(a, rd.blk[c], rd.g[c],
+                    crc_tiny(rd.g[c].ptr(), rd.g[c].len, rd.g[c].s0));
         }
         if (rd.g[c].kind == kRagSkip && lane == 0) lds[kFlag] = 1;
       }
@@ -543,7 +406,7 @@ __device__ __forceinline__ void ragged_run(const KernelArgs& a, const uint32_t* 
     rd.issue(k, lane);
   }
 
-  // 6. Blocks over kLongBytes in this run (rare)
+  // 6. Blocks over long_split in this run (rare)
   ragged_long_pass<W>(a, zpow, lds, start, n, keys, lane_base, src);
 }
 

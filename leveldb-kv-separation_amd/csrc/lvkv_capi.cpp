@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "crc32c_modes.h"
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
 #include "lvkv_launch.h"
@@ -227,13 +228,10 @@ int run_batch(KernelArgs a, size_t nblocks, hipStream_t stream) {
                                         groups, stream);
       else
         e = launch_crc32c_uniform(uniform_args(*c, b), 0, groups, stream);
-    } else if (b.offsets != nullptr && b.mode != kModeLogVerify && b.mode != kModeLogFill) {
-      // Blocks longer than kLongBytes go to one workgroup each (segments in
-      // parallel) instead of one wave; the main kernel leaves them alone.
-      b.long_split = kLongBytes;
-      e = launch_crc32c_general(b, c->groups, stream);
-    } else if (b.offsets != nullptr) {  // log headers
-      b.long_split = kLogLongBytes;
+    } else if (b.offsets != nullptr) {
+      // Blocks longer than the mode's bound go to one workgroup each
+      // (segments in parallel) instead of one wave.
+      b.long_split = mode_long_split(b.mode);
       e = launch_crc32c_general(b, c->groups, stream);
     } else {  // uniform layout, block ends not 4-byte aligned
       e = launch_crc32c_batch(b, false, groups, stream);

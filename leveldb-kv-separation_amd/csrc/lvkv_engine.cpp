@@ -47,6 +47,7 @@
 #include <algorithm>
 #include <mutex>
 
+#include "crc32c_modes.h"
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
 #include "lvkv_tables.h"
@@ -701,8 +702,8 @@ int dispatch(Engine& e, const EngineKernel& k, const void* args, size_t size, ui
 int submit_general(Engine& eng, KernelArgs a, size_t nblocks, uint32_t flags) {
   Engine* e = &eng;
   if (nblocks == 0) return LVKV_OK;
-  const bool log = a.mode == kModeLogVerify || a.mode == kModeLogFill;
-  a.long_split = log ? kLogLongBytes : kLongBytes;
+  const bool log = mode_is_log(a.mode);
+  a.long_split = mode_long_split(a.mode);
   a.row_tab = e->d_tables;
   a.lane_tab = e->d_tables + kRowTabDwords;
   std::lock_guard<std::mutex> lk(e->mu);

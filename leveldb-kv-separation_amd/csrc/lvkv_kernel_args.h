@@ -51,7 +51,8 @@ constexpr uint32_t kLdsBytes = 160 * 1024;
 constexpr uint32_t kCastagnoliReflected = 0x82f63b78u;
 constexpr uint32_t kMaskDelta = 0xa282ead8u;  // util/crc32c.h:22
 
-// Kernel modes (KernelArgs::mode).
+// Kernel modes (KernelArgs::mode). What each one covers, checks and stores
+// is stated once, in crc32c_modes.h.
 enum : uint32_t {
   kModeCompute = 0,    // out_crc[i] = Extend(init_i, base + off_i, len_i)
   kModeSstVerify = 1,  // table/format.cc:92-99: covers n+1, trailer after it
@@ -62,18 +63,16 @@ enum : uint32_t {
                        // masked CRC into header bytes 0..3
   kModeSstTable = 5,   // kModeSstVerify whose store also merges the index
                        // parse status (out_status in), the type byte and
-                       // the per-table totals (sst_reports)
-  kModeLogStaged = 6,  // kModeLogVerify over the WAL walk's staged headers
-                       // (lvkv_log_blocks.hip): out_crc, out_status (1 =
-                       // mismatch), and on a mismatch the lowest staged
-                       // index per 32 KiB block into log_first_bad[hdr >> 15]
+                       // the per-table totals (sst_reports); the ragged
+                       // walk alone serves it
 };
 
 struct KernelArgs {
   const uint8_t* base;        // device bytes all offsets are relative to
   const uint64_t* offsets;    // per-block offsets; nullptr = uniform stride
   const uint32_t* lengths;    // per-block lengths (ignored in uniform mode)
-  const uint32_t* inits;      // per-block init CRCs; nullptr = `init`
+  const uint32_t* inits;      // per-block init CRCs (per-block layout only);
+                              // nullptr = `init`
   uint64_t stride;            // uniform mode: block i at base + i*stride
   uint32_t length;            // uniform mode length
   uint32_t init;              // init CRC when inits == nullptr
@@ -87,8 +86,8 @@ struct KernelArgs {
   uint32_t long_split;        // non-zero: blocks whose covered length
                               // exceeds it (bytes) are walked by a whole
                               // workgroup (crc32c_ragged.hip) or left to
-                              // crc32c_long_kernel (crc32c_kernel.hip, which
-                              // takes kLongBytes whatever the value)
+                              // crc32c_long_kernel (crc32c_kernel.hip skips
+                              // them; both compare with this value)
   uint64_t* stamps;           // probe builds only: per-wave timestamps
   const uint32_t* count;      // optional device-side block count: the launch
                               // covers min(nblocks, *count) blocks (a count
@@ -96,15 +95,8 @@ struct KernelArgs {
                               // parse); nullptr = nblocks
   void* sst_reports;          // kModeSstTable: lvkv_sst_report[sst_ntables]
   uint32_t sst_ntables;
-  uint32_t run_units;         // with run_base: workgroup g of G walks blocks
-  const uint32_t* run_base;   //   [run_base[gU/G], run_base[(g+1)U/G]) (the
-                              //   last one to the count): runs balanced in
-                              //   bytes when a unit is a fixed-size region
-                              //   (the WAL's 32 KiB blocks); nullptr = equal
-                              //   block counts per workgroup
   uint32_t fresh_desc;        // 1: offsets/lengths were written by this same
                               //   launch (vector loads after an acquire)
-  uint32_t* log_first_bad;    // kModeLogStaged: per 32 KiB block (atomicMin)
   int32_t general_cfg;        // host side: kernel of general-layout batches
   int32_t log_cfg;            //   and of WAL records (launch_crc32c_general);
                               //   the device context's choice, never read

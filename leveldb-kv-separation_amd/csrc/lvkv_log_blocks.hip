@@ -244,11 +244,7 @@ __device__ __forceinline__ void lds_record_crcs(const uint8_t* buf, const uint32
 
 // Bitwise register update over n (< 4) bytes from `reg` (lane-uniform).
 __device__ __forceinline__ uint32_t tiny_reg(const uint8_t* p, uint32_t n, uint32_t reg) {
-  for (uint32_t i = 0; i < n; ++i) {
-    reg ^= p[i];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) reg = (reg >> 1) ^ (kCastagnoliReflected & (0u - (reg & 1u)));
-  }
+  for (uint32_t i = 0; i < n; ++i) reg = crc_byte_bitwise(reg, p[i]);
   return reg;
 }
 

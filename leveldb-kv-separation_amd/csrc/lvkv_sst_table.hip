@@ -840,7 +840,7 @@ __global__ void __launch_bounds__(64 * kFW, 2)
   if (blockIdx.x == ntables) sst_stamp(stamps, 0, 10);
   // Wait for every head, then one agent-scope acquire (pairing with the
   // heads' release of done_). Everything the heads wrote is also read with
-  // agent-scope atomic loads (desc_u64/_u32, the kModeSstTable store).
+  // agent-scope atomic loads (mode_covered<true>, the kModeSstTable store).
   if (wave == 0) {
     for (uint32_t j = lane; j < ntables; j += 64)
       while (__hip_atomic_load(&reports[j].done_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != gen)
@@ -902,16 +902,14 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v) {
 }
 
 // The walk's blocks: the pass's decoded entries in LDS; its results go back
-// there (CRC, ReadBlock's verdict merged as rag_store's kModeSstTable does).
+// there (CRC, ReadBlock's verdict merged as mode_store's kModeSstTable does).
 struct SpecSrc {
   SpecLds* L;
   uint64_t img;  // the table image's address
   // the stored CRC after each block: loaded by the walk (RagRound::adopt)
   __device__ __forceinline__ bool trailer(const KernelArgs&) const { return true; }
   __device__ __forceinline__ RagBlock block(const KernelArgs& a, uint32_t b, bool live) const {
-    RagBlock g;
-    g.ptr_lo = g.ptr_hi = g.len = g.s0 = g.expected = 0;
-    g.kind = kRagNone;
+    RagBlock g = rag_none();
     if (!live) return g;
     if (__builtin_amdgcn_readfirstlane(L->st[b]) != LVKV_BLOCK_OK) return g;
     const uint64_t o = L->off[b];
@@ -923,7 +921,7 @@ struct SpecSrc {
     g.ptr_hi = static_cast<uint32_t>(ptr >> 32);
     g.len = len;
     g.s0 = 0xffffffffu;  // init 0
-    g.kind = len > a.long_split ? kRagSkip : len < 4 ? kRagTiny : kRagRows;
+    g.kind = rag_kind(len, a.long_split);
     return g;
   }
   __device__ __forceinline__ void store(const KernelArgs&, uint32_t b, const RagBlock& g,
@@ -1220,11 +1218,10 @@ hipError_t launch_sst_tables(const uint8_t* file, const uint64_t* toff, const ui
   a.mode = kModeSstTable;
   a.nblocks = capacity;
   a.count = &reports[0].total_;
-  a.long_split = kLongBytes;  // large data/filter blocks: one workgroup each
+  a.long_split = mode_long_split(a.mode);  // large data/filter blocks: one workgroup each
   a.sst_reports = reports;
   a.sst_ntables = ntables;
   if (form == kSstFormSpec && ntables < static_cast<uint32_t>(groups)) {
-    a.run_base = nullptr;
     // two workgroups per CU resident: the heads, then 2 * groups - ntables
     // CRC workgroups (more than ntables)
     const uint32_t grid = 2u * static_cast<uint32_t>(groups);
