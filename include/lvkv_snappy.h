@@ -326,6 +326,85 @@ int lvkv_sst_build_blocks_device(
     uint64_t* d_raw_off, uint32_t* d_raw_len, size_t max_blocks,
     lvkv_sst_build_report* d_report, void* stream);
 
+/* ---- the entries of decoded data blocks: Block::Iter's walk on the device ---- */
+
+/* per block (d_block_status) */
+#define LVKV_ENTRIES_OK 0
+#define LVKV_ENTRIES_BAD_BLOCK 1   /* "bad block contents" (table/block.cc:25-40, 281-284) */
+#define LVKV_ENTRIES_BAD_ENTRY 2   /* "bad entry in block" (table/block.cc:243-249) */
+#define LVKV_ENTRIES_SKIPPED 3     /* d_skip[b] != 0: not walked */
+/* report.status */
+#define LVKV_ENTRIES_CAPACITY 1    /* more entries than max_entries or more key bytes than
+                                      key_capacity */
+
+typedef struct lvkv_sst_entries_report {
+  int32_t  status;          /* 0, or LVKV_ENTRIES_CAPACITY */
+  uint32_t nbad;            /* blocks with BAD_BLOCK or BAD_ENTRY */
+  uint32_t first_bad_block; /* lowest such block, else 0xFFFFFFFF */
+  uint32_t max_key_len;
+  uint64_t num_entries;     /* with CAPACITY: the number needed */
+  uint64_t key_bytes;       /* end of the last key in d_keys; with CAPACITY: the bytes needed */
+  uint64_t value_bytes;     /* sum of the value lengths */
+} lvkv_sst_entries_report;
+
+/* The scratch of lvkv_sst_read_entries_device for nblocks blocks of
+ * total_raw_bytes in all; it never decreases when an argument grows. The call
+ * itself knows no total: it needs at least the value for total_raw_bytes 0,
+ * and a block whose restart runs find no room in a smaller scratch than the
+ * batch's total asks for is walked by one lane (slower, the same result). */
+size_t lvkv_sst_read_entries_scratch_bytes(size_t nblocks, uint64_t total_raw_bytes);
+
+/*
+ * The inverse of lvkv_sst_build_blocks_device, in one stream-ordered call:
+ * the decoded data blocks d_raw[d_raw_off[b], + d_raw_len[b]) -- the d_out,
+ * d_out_off and d_out_len of lvkv_sst_read_blocks_device; d_skip (may be
+ * null) is that call's d_status, and a block with d_skip[b] != 0 is SKIPPED
+ * and not read -- become the entries Block::NewIterator + SeekToFirst + Next
+ * until !Valid() hand out (table/block.cc:77-279), block after block, in the
+ * layout the build call takes. Entries d_block_first[b] .. d_block_first[b +
+ * 1] are block b's. Key i is the restored key (shared prefix + delta) at
+ * d_keys[d_key_off[i], + d_key_len[i]); d_key_off[0] = 0 and d_key_off[i] =
+ * the end of key i - 1 rounded up to 8 (the bytes between keys are not
+ * written). Values are not copied: d_val_off[i] is the value's offset in
+ * d_raw, which the caller passes as the build's d_vals.
+ *
+ * The verdicts are the walk's and nothing stricter. A block under 4 bytes or
+ * with a restart count above (len - 4) / 4 is BAD_BLOCK and has no entries; a
+ * restart count of 0 is OK with no entries (NewEmptyIterator). The walk
+ * starts at restart[0], which need not be 0 and may lie at or past the
+ * entries' end (OK, no entries), and never looks at restart[1..]: restart
+ * arrays that lie change nothing. An entry DecodeEntry refuses (fewer than 3
+ * bytes before the restart array, a varint that runs out or is too long, a
+ * delta and value that pass the restart array) or whose shared exceeds the
+ * previous key's length ends the walk with BAD_ENTRY; the entries before it
+ * are emitted.
+ *
+ * One deliberate difference: DecodeEntry adds non_shared + value_length in 32
+ * bits (table/block.cc:71), and a sum that wraps lets the reference read far
+ * outside the block. Here the sum is taken in 64 bits and the entry is
+ * BAD_ENTRY.
+ *
+ * No synchronisation, no copy to the host: d_report (device memory) says how
+ * it went. d_block_first, d_block_status and the report are always written.
+ * With LVKV_ENTRIES_CAPACITY nothing is written to d_keys or the four entry
+ * arrays (the counts are known before the first byte is copied) and
+ * num_entries and key_bytes are what a repeat needs; never anything at or
+ * past d_keys + key_capacity or slot max_entries of the arrays.
+ *
+ * nblocks == 0, before every other check: LVKV_OK, and a report of no entries
+ * where d_report is not null (every pointer may be null). LVKV_ERR_INVALID,
+ * before any launch: a null pointer other than d_skip, nblocks >= 2^31,
+ * scratch_bytes under the sizing function's value for total_raw_bytes 0.
+ */
+int lvkv_sst_read_entries_device(
+    const void* d_raw, const uint64_t* d_raw_off, const uint32_t* d_raw_len,
+    const uint8_t* d_skip /* may be null */, size_t nblocks,
+    void* d_scratch, size_t scratch_bytes,
+    void* d_keys, uint64_t key_capacity, uint64_t* d_key_off, uint32_t* d_key_len,
+    uint64_t* d_val_off, uint32_t* d_val_len, size_t max_entries,
+    uint64_t* d_block_first /* nblocks + 1 */, uint8_t* d_block_status,
+    lvkv_sst_entries_report* d_report, void* stream);
+
 /* ReadBlock verdicts */
 #define LVKV_READ_OK 0
 #define LVKV_READ_CHECKSUM 1        /* "block checksum mismatch" (table/format.cc:95-98) */

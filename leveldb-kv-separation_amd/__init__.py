@@ -189,6 +189,11 @@ def _load() -> ctypes.CDLL:
     L.lvkv_sst_build_blocks_device.restype = i32
     L.lvkv_sst_read_blocks_device.argtypes = [vp, vp, vp, sz, i32, vp, vp, vp, vp, vp, u32, vp]
     L.lvkv_sst_read_blocks_device.restype = i32
+    L.lvkv_sst_read_entries_scratch_bytes.argtypes = [sz, u64]
+    L.lvkv_sst_read_entries_scratch_bytes.restype = sz
+    L.lvkv_sst_read_entries_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, u64, vp, vp, vp, vp,
+                                               sz, vp, vp, vp, vp]
+    L.lvkv_sst_read_entries_device.restype = i32
     L.lvkv_strerror.argtypes = [i32]
     L.lvkv_strerror.restype = ctypes.c_char_p
     L.lvkv_last_hip_error.argtypes = []
@@ -1037,6 +1042,108 @@ def sst_read_blocks(file, handle_off, handle_size, *, max_ulen: int, verify: boo
                 _stream_handle(stream, dev))
         _check("lvkv_sst_read_blocks_device", rc)
     return out, out_offsets, out_len, status
+
+
+ENTRIES_OK, ENTRIES_BAD_BLOCK, ENTRIES_BAD_ENTRY, ENTRIES_SKIPPED = range(4)
+ENTRIES_CAPACITY = 1
+
+
+class SstEntriesReport(ctypes.Structure):
+    """lvkv_sst_entries_report (include/lvkv_snappy.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("nbad", ctypes.c_uint32),
+                ("first_bad_block", ctypes.c_uint32), ("max_key_len", ctypes.c_uint32),
+                ("num_entries", ctypes.c_uint64), ("key_bytes", ctypes.c_uint64),
+                ("value_bytes", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def sst_read_entries(raw, raw_off, raw_len, *, skip=None, keys=None,
+                     key_capacity: Optional[int] = None, max_entries: Optional[int] = None,
+                     stream=None):
+    """Block::Iter's forward walk over decoded data blocks
+    (lvkv_sst_read_entries_device): blocks raw[raw_off[b] : raw_off[b] +
+    raw_len[b]] -- sst_read_blocks' out, out_offsets and lengths; skip: its
+    status, a block with a non-zero byte is not walked -- become their
+    entries, in block order, laid out as sst_build_blocks takes them: the
+    restored keys in `keys` 8 bytes apart, the values left in `raw`.
+    max_entries defaults to the most the bytes can hold (an entry takes three).
+    Without key_capacity the keys get a first guess of the blocks' bytes and
+    the call is repeated once with what the report asks for. Returns (keys,
+    key_off int64, key_len int32, raw, val_off int64, val_len int32 -- the
+    build's inputs, cut to report['num_entries'] -- block_first int64 of
+    nblocks + 1, block_status uint8 ENTRIES_*, report dict). report['status']
+    is 0 or ENTRIES_CAPACITY, and nothing of the entries is written unless it
+    is 0. The report is the one thing read back."""
+    torch = _torch()
+    n = raw_off.numel()
+    dev = raw.device
+    if raw_len.numel() != n or (skip is not None and skip.numel() != n):
+        raise ValueError("the block arrays differ in length")
+    total = int(raw_len.to(torch.int64).sum().item()) if n else 0
+    if max_entries is None:
+        max_entries = total // 3
+    guess = key_capacity is None and keys is None
+    if key_capacity is None:
+        key_capacity = keys.numel() if keys is not None else 2 * total + 64
+    scratch = torch.empty(int(_lib.lvkv_sst_read_entries_scratch_bytes(n, total)),
+                          dtype=torch.uint8, device=dev)
+    slots = max(1, max_entries)
+    key_off = torch.empty(slots, dtype=torch.int64, device=dev)
+    key_len = torch.empty(slots, dtype=torch.int32, device=dev)
+    val_off = torch.empty(slots, dtype=torch.int64, device=dev)
+    val_len = torch.empty(slots, dtype=torch.int32, device=dev)
+    first = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(max(1, n), dtype=torch.uint8, device=dev)[:n]
+    rep = torch.zeros(ctypes.sizeof(SstEntriesReport), dtype=torch.uint8, device=dev)
+    b8 = (torch.uint8, torch.int8)
+    for attempt in range(2):
+        if keys is None or keys.numel() < key_capacity:
+            keys = torch.empty(max(8, key_capacity), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lvkv_sst_read_entries_device(
+                _dev_ptr(raw, "raw", b8) if n else None,
+                _dev_ptr(raw_off, "raw_off", (torch.int64,)) if n else None,
+                _dev_ptr(raw_len, "raw_len", (torch.int32,)) if n else None,
+                _dev_ptr(skip, "skip", (torch.uint8,)) if skip is not None and n else None, n,
+                _dev_ptr(scratch, "scratch", b8), scratch.numel(), _dev_ptr(keys, "keys", b8),
+                int(key_capacity), _dev_ptr(key_off, "key_off"), _dev_ptr(key_len, "key_len"),
+                _dev_ptr(val_off, "val_off"), _dev_ptr(val_len, "val_len"), int(max_entries),
+                _dev_ptr(first, "block_first"), _dev_ptr(status, "block_status") if n else None,
+                _dev_ptr(rep, "report"), _stream_handle(stream, dev))
+        _check("lvkv_sst_read_entries_device", rc)
+        if stream is not None:
+            stream.synchronize()
+        report = SstEntriesReport.from_buffer_copy(bytes(rep.cpu().numpy())).as_dict()
+        if not (guess and attempt == 0 and report["status"] == ENTRIES_CAPACITY and
+                report["num_entries"] <= max_entries):
+            break
+        key_capacity, keys = report["key_bytes"], None
+    ne = report["num_entries"] if report["status"] == 0 else 0
+    return (keys, key_off[:ne], key_len[:ne], raw, val_off[:ne], val_len[:ne], first, status,
+            report)
+
+
+def sst_read_table(file, *, filter_policy: Optional[str] = None, max_ulen: int,
+                   verify: bool = True, stream=None):
+    """A table image -> its entries, ready for sst_build_table: sst_verify_table
+    (footer, index: the data blocks' handles), sst_read_blocks over them
+    (max_ulen: the longest decoded block), sst_read_entries over what that
+    decoded. The reports are read on the host between the calls. Returns
+    (keys, key_off, key_len, vals, val_off, val_len, table report, block
+    status uint8 READ_*, entries report); the first six are None when the
+    table's status is not 0 (nothing to list the blocks from). A block
+    ReadBlock refused is skipped (ENTRIES_SKIPPED is not among the entries
+    report's nbad: look at the block status)."""
+    table, off, size, _, _ = sst_verify_table(file, filter_policy=filter_policy, stream=stream)
+    if table["status"] != 0:
+        return (None,) * 6 + (table, None, None)
+    nd = table["ndata"]
+    out, out_off, out_len, rstatus = sst_read_blocks(file, off[:nd], size[:nd], max_ulen=max_ulen,
+                                                     verify=verify, stream=stream)
+    e = sst_read_entries(out, out_off, out_len, skip=rstatus, stream=stream)
+    return e[:6] + (table, rstatus, e[8])
 
 
 class LogReport(ctypes.Structure):

@@ -1,6 +1,7 @@
 // The workgroup-wide exclusive scan of the table writers, one pass and many
 // (lvkv_sst_blocks.hip's slot and layout kernels, lvkv_sst_finish.hip's
-// filter and index layouts, lvkv_sst_build.hip's device-wide scan).
+// filter and index layouts, lvkv_sst_build.hip's device-wide scan,
+// lvkv_sst_entries.hip's report).
 #ifndef LVKV_BLOCK_SCAN_H_
 #define LVKV_BLOCK_SCAN_H_
 

@@ -1110,6 +1110,54 @@ int lvkv_sst_build_blocks_device(const void* d_keys, const uint64_t* d_key_off,
   return e == hipSuccess ? LVKV_OK : hip_fail(e);
 }
 
+size_t lvkv_sst_read_entries_scratch_bytes(size_t nblocks, uint64_t total_raw_bytes) {
+  return sst_entries_scratch_bytes(nblocks, total_raw_bytes);
+}
+
+int lvkv_sst_read_entries_device(const void* d_raw, const uint64_t* d_raw_off,
+                                 const uint32_t* d_raw_len, const uint8_t* d_skip, size_t nblocks,
+                                 void* d_scratch, size_t scratch_bytes, void* d_keys,
+                                 uint64_t key_capacity, uint64_t* d_key_off, uint32_t* d_key_len,
+                                 uint64_t* d_val_off, uint32_t* d_val_len, size_t max_entries,
+                                 uint64_t* d_block_first, uint8_t* d_block_status,
+                                 lvkv_sst_entries_report* d_report, void* stream) {
+  SstEntriesArgs a{};
+  a.report = d_report;
+  if (nblocks == 0) {
+    if (!d_report) return LVKV_OK;
+    int rc = LVKV_OK;
+    if (current_ctx(&rc) == nullptr) return rc;
+    const hipError_t e = launch_sst_entries(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? LVKV_OK : hip_fail(e);
+  }
+  if (!d_raw || !d_raw_off || !d_raw_len || !d_scratch || !d_keys || !d_key_off || !d_key_len ||
+      !d_val_off || !d_val_len || !d_block_first || !d_block_status || !d_report)
+    return LVKV_ERR_INVALID;
+  if (nblocks >= (uint64_t{1} << 31) ||
+      scratch_bytes < lvkv_sst_read_entries_scratch_bytes(nblocks, 0))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  a.raw = static_cast<const uint8_t*>(d_raw);
+  a.raw_off = d_raw_off;
+  a.raw_len = d_raw_len;
+  a.skip = d_skip;
+  a.nblocks = static_cast<uint32_t>(nblocks);
+  a.scratch = static_cast<uint8_t*>(d_scratch);
+  a.scratch_bytes = scratch_bytes;
+  a.keys = static_cast<uint8_t*>(d_keys);
+  a.key_capacity = key_capacity;
+  a.key_off = d_key_off;
+  a.key_len = d_key_len;
+  a.val_off = d_val_off;
+  a.val_len = d_val_len;
+  a.max_entries = max_entries;
+  a.block_first = d_block_first;
+  a.block_status = d_block_status;
+  const hipError_t e = launch_sst_entries(a, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
 int lvkv_sst_write_blocks_device(const void* d_raw, const uint64_t* d_raw_off,
                                  const uint32_t* d_raw_len, size_t nblocks, int compression,
                                  uint32_t max_len, void* d_scratch, void* d_file,

@@ -266,6 +266,45 @@ struct SstBuildArgs {
   lvkv_sst_build_report* report;
 };
 hipError_t launch_sst_build(const SstBuildArgs& a, hipStream_t stream);
+// The device-wide exclusive scan of n u64 in place, the total at [n], of a0
+// and (when not null) a1 at once: three launches. sums: scan_sums_words(n)
+// words the launches hand their tile sums over in.
+constexpr uint32_t kScanTile = 4096;  // items a workgroup
+constexpr uint64_t scan_sums_words(uint64_t n) { return 2 * ((n + kScanTile - 1) / kScanTile); }
+hipError_t launch_exclusive_scan(uint64_t* a0, uint64_t* a1, uint64_t* sums, uint32_t n,
+                                 hipStream_t stream);
+
+// ---- Block::Iter's forward walk on the device (lvkv_sst_entries.hip) --------
+
+// The fewest bytes a restart run takes in a block: a restart and an entry.
+constexpr uint64_t kEntriesRunBytes = 7;
+// Bytes of the running key a group of the write kernel keeps in LDS; the bytes
+// of a longer key past them are traced back to the delta they came from.
+constexpr uint32_t kEntriesKeyWindow = 512;
+// lvkv_sst_read_entries_scratch_bytes: the per-block arrays and a slot for
+// every run total_raw_bytes can hold. The call gives the runs whatever its
+// scratch_bytes leave beyond the arrays.
+size_t sst_entries_scratch_bytes(size_t nblocks, uint64_t total_raw_bytes);
+struct SstEntriesArgs {
+  const uint8_t* raw;
+  const uint64_t* raw_off;
+  const uint32_t* raw_len;
+  const uint8_t* skip;  // may be null
+  uint32_t nblocks;
+  uint8_t* scratch;
+  uint64_t scratch_bytes;
+  uint8_t* keys;
+  uint64_t key_capacity;
+  uint64_t* key_off;
+  uint32_t* key_len;
+  uint64_t* val_off;
+  uint32_t* val_len;
+  uint64_t max_entries;
+  uint64_t* block_first;  // nblocks + 1
+  uint8_t* block_status;
+  lvkv_sst_entries_report* report;
+};
+hipError_t launch_sst_entries(const SstEntriesArgs& a, hipStream_t stream);
 
 #ifdef LVKV_PROBE_BUILD
 // Probe builds (tools/probe/liblvkv_probe.so): timestamp buffers and knobs

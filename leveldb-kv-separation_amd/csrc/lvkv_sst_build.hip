@@ -41,7 +41,6 @@ namespace lvkv {
 namespace {
 
 constexpr uint32_t kNone = 0xffffffffu;
-constexpr uint32_t kScanTile = 4096;   // items a workgroup of the device-wide scan
 constexpr uint32_t kDoublings = 12;    // 2^12 hops cover a tile
 static_assert((1u << kDoublings) >= kBuildTile, "a chain has up to kBuildTile links in a tile");
 static_assert(kBuildTile % 1024 == 0, "four entries a thread");
@@ -199,7 +198,8 @@ __global__ void __launch_bounds__(256) build_entry_kernel(Dev d) {
 
 // ---- the device-wide exclusive scan: n items in place, the total at [n] ------
 // blockIdx.y picks the array; three launches, a kernel boundary where a
-// workgroup needs another's sum.
+// workgroup needs another's sum. launch_exclusive_scan (below, declared in
+// lvkv_launch.h) is lvkv_sst_entries.hip's scan as well.
 
 struct ScanArgs {
   uint64_t* a[2];
@@ -429,7 +429,10 @@ __global__ void __launch_bounds__(256) build_write_kernel(Dev d) {
   }
 }
 
-hipError_t scan(uint64_t* a0, uint64_t* a1, uint64_t* sums, uint32_t n, hipStream_t stream) {
+}  // namespace
+
+hipError_t launch_exclusive_scan(uint64_t* a0, uint64_t* a1, uint64_t* sums, uint32_t n,
+                                 hipStream_t stream) {
   ScanArgs s{};
   s.a[0] = a0;
   s.a[1] = a1;
@@ -442,6 +445,8 @@ hipError_t scan(uint64_t* a0, uint64_t* a1, uint64_t* sums, uint32_t n, hipStrea
   hipLaunchKernelGGL(scan_apply_kernel, dim3(s.tiles, arrays), dim3(1024), 0, stream, s);
   return hipGetLastError();
 }
+
+namespace {
 
 // The call's scratch, listed once: the control words, then the arrays, each
 // rounded up to 16 bytes. Returns the bytes from `base` (null: sizing only).
@@ -457,7 +462,7 @@ uint64_t carve(Dev& d, uint8_t* base, uint64_t n) {
   d.exit = c.take<uint32_t>(n, 16);
   d.bstart = c.take<uint32_t>(n, 16);
   d.entry = c.take<uint32_t>((n + kBuildTile - 1) / kBuildTile, 16);
-  d.sums = c.take<uint64_t>(2 * ((n + kScanTile - 1) / kScanTile), 16);  // the scans' tile sums
+  d.sums = c.take<uint64_t>(scan_sums_words(n), 16);
   return c.bytes();
 }
 
@@ -498,15 +503,15 @@ hipError_t launch_sst_build(const SstBuildArgs& a, hipStream_t stream) {
   const uint32_t per_entry = (n + 255u) / 256u, tiles = (n + kBuildTile - 1u) / kBuildTile;
   hipLaunchKernelGGL(build_init_kernel, dim3(1), dim3(64), 0, stream, d.ctl);
   hipLaunchKernelGGL(build_entry_kernel, dim3(per_entry), dim3(256), 0, stream, d);
-  hipError_t e = scan(d.ea, d.ed, d.sums, n, stream);
+  hipError_t e = launch_exclusive_scan(d.ea, d.ed, d.sums, n, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(build_exit_kernel, dim3(tiles), dim3(1024), 0, stream, d);
   hipLaunchKernelGGL(build_hop_kernel, dim3(1), dim3(64), 0, stream, d);
   hipLaunchKernelGGL(build_mark_kernel, dim3(tiles), dim3(1024), 0, stream, d);
-  e = scan(d.ef, nullptr, d.sums, n, stream);
+  e = launch_exclusive_scan(d.ef, nullptr, d.sums, n, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(build_block_kernel, dim3(per_entry), dim3(256), 0, stream, d);
-  e = scan(d.eb, nullptr, d.sums, n, stream);
+  e = launch_exclusive_scan(d.eb, nullptr, d.sums, n, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(build_report_kernel, dim3(1), dim3(64), 0, stream, d);
   const uint64_t write_groups = (uint64_t{n} * kWriteLanes + 255u) / 256u;
