@@ -405,6 +405,106 @@ int lvkv_sst_read_entries_device(
     uint64_t* d_block_first /* nblocks + 1 */, uint8_t* d_block_status,
     lvkv_sst_entries_report* d_report, void* stream);
 
+/* ---- merging sorted runs of entries: MergingIterator and compaction's drops ---- */
+
+#define LVKV_MERGE_OK 0
+#define LVKV_MERGE_UNSORTED 1     /* entry first_bad_entry is not greater than the one before it
+                                     in its run */
+#define LVKV_MERGE_BAD_KEY 2      /* key_format 1 and a key under 8 bytes */
+#define LVKV_MERGE_CAPACITY 3     /* more survivors than max_out */
+#define LVKV_MERGE_BAD_RUNS 4     /* d_run_first does not go from 0 to nentries without descending */
+
+#define LVKV_MERGE_MAX_RUNS 64
+#define LVKV_MERGE_COMPACT 1u     /* flags: apply DoCompactionWork's drops (key_format 1 only) */
+
+typedef struct lvkv_sst_merge_report {
+  int32_t  status;
+  uint32_t first_bad_entry;   /* lowest offending input entry for UNSORTED / BAD_KEY, else
+                                 0xFFFFFFFF */
+  uint32_t num_in;            /* nentries */
+  uint32_t num_out;           /* survivors; with CAPACITY: the max_out a repeat needs */
+  uint32_t num_hidden;        /* dropped: hidden by a newer entry of the same user key */
+  uint32_t num_obsolete;      /* dropped: deletions nothing needs any more */
+  uint32_t max_key_len;       /* longest input key */
+  uint32_t reserved_;         /* 0 */
+  uint64_t key_bytes;         /* sum of the survivors' key lengths */
+  uint64_t value_bytes;       /* sum of the survivors' value lengths */
+} lvkv_sst_merge_report;
+
+/* The scratch of lvkv_sst_merge_entries_device; it never decreases when an
+ * argument grows. */
+size_t lvkv_sst_merge_entries_scratch_bytes(size_t nentries, uint32_t nruns);
+
+/*
+ * What a compaction does between lvkv_sst_read_entries_device and
+ * lvkv_sst_build_blocks_device, in one stream-ordered call. The six entry
+ * arrays are the build call's, and hold nruns sorted runs laid end to end:
+ * run r is entries [d_run_first[r], d_run_first[r + 1]) (d_run_first: u64
+ * [nruns + 1] in device memory, d_run_first[0] = 0, never descending, the
+ * last word nentries -- anything else is LVKV_MERGE_BAD_RUNS; empty runs are
+ * legal anywhere). Inside a run every key is greater than the one before it,
+ * under the build call's comparators: key_format 0 byte-wise, 1
+ * InternalKeyComparator (db/dbformat.cc:47-63) with every key 8 bytes or
+ * longer. A level's files laid end to end are one run.
+ *
+ * The order is MergingIterator's forward walk (table/merger.cc:150-163): the
+ * smallest key of the runs' heads comes next, among equal keys the run of
+ * the lowest index. Equal keys in different runs are legal and all come out.
+ *
+ * The drops, only with LVKV_MERGE_COMPACT in flags (key_format 1): the loop of
+ * DBImpl::DoCompactionWork (db/db_impl.cc:1022-1055) over that order. With
+ * last = the sequence of the entry directly before in merged order where that
+ * entry parses (type byte <= 1) and has the same user key -- dropped itself or
+ * not -- and kMaxSequenceNumber otherwise: a key that does not parse is never
+ * dropped; an entry is hidden when last <= smallest_snapshot; a deletion that
+ * is not hidden is obsolete when its sequence is <= smallest_snapshot and its
+ * user key lies in none of the n_deeper ranges [smallest, largest] of user
+ * keys, bounds included, byte-wise (Compaction::IsBaseLevelForKey,
+ * db/version_set.cc:1518-1537: the files of levels level + 2 and deeper, in
+ * any order, overlapping or not). Range g is d_deeper_keys[d_deeper_off[2g],
+ * + d_deeper_len[2g]) .. d_deeper_keys[d_deeper_off[2g + 1], + d_deeper_len[2g
+ * + 1]). As in the reference, a smallest_snapshot of kMaxSequenceNumber (2^56
+ * - 1) or more hides every entry that parses, a user key's first included.
+ *
+ * No key or value byte is copied. Survivor j, in merged order, is input entry
+ * d_out_src[j], and d_out_key_off / d_out_key_len / d_out_val_off /
+ * d_out_val_len [j] are that entry's own descriptors into d_keys and d_vals:
+ * with those two buffers they are the build call's arguments. d_dropped_src
+ * (u32 [nentries], may be null) lists the dropped entries' input indices in
+ * merged order, num_hidden + num_obsolete of them (what a caller that keeps
+ * values elsewhere marks invalid, db/db_impl.cc:1126-1135).
+ *
+ * No synchronisation, no copy to the host: d_report (device memory) says how
+ * it went. BAD_RUNS is reported before BAD_KEY, that before UNSORTED, that
+ * before CAPACITY; first_bad_entry is the lowest entry of the reported kind (a
+ * pair that descends across a run boundary is no error). On a status other
+ * than OK nothing at all is written to the five output arrays or to
+ * d_dropped_src (the order and the counts are known before the first word is
+ * stored), and never anything at or past slot max_out. num_in always holds;
+ * max_key_len with every status but BAD_RUNS; the counts and sums with OK and
+ * CAPACITY, and are 0 otherwise.
+ *
+ * nentries == 0, before every other check: LVKV_OK, and a report of no
+ * entries where d_report is not null (every pointer may be null).
+ * LVKV_ERR_INVALID, before any launch: a null pointer other than
+ * d_dropped_src (and the three d_deeper arrays when n_deeper is 0), nruns
+ * outside 1..LVKV_MERGE_MAX_RUNS, key_format outside 0..1, a flag other than
+ * LVKV_MERGE_COMPACT, LVKV_MERGE_COMPACT with key_format 0, nentries or
+ * n_deeper >= 2^31, scratch_bytes under the sizing function's value.
+ */
+int lvkv_sst_merge_entries_device(
+    const void* d_keys, const uint64_t* d_key_off, const uint32_t* d_key_len,
+    const void* d_vals, const uint64_t* d_val_off, const uint32_t* d_val_len, size_t nentries,
+    const uint64_t* d_run_first /* nruns + 1 */, uint32_t nruns, int key_format, uint32_t flags,
+    uint64_t smallest_snapshot,
+    const void* d_deeper_keys, const uint64_t* d_deeper_off, const uint32_t* d_deeper_len,
+    size_t n_deeper,
+    void* d_scratch, size_t scratch_bytes,
+    uint64_t* d_out_key_off, uint32_t* d_out_key_len, uint64_t* d_out_val_off,
+    uint32_t* d_out_val_len, uint32_t* d_out_src, size_t max_out,
+    uint32_t* d_dropped_src /* nentries, may be null */,
+    lvkv_sst_merge_report* d_report, void* stream);
+
 /* ReadBlock verdicts */
 #define LVKV_READ_OK 0
 #define LVKV_READ_CHECKSUM 1        /* "block checksum mismatch" (table/format.cc:95-98) */

@@ -194,6 +194,12 @@ def _load() -> ctypes.CDLL:
     L.lvkv_sst_read_entries_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, u64, vp, vp, vp, vp,
                                                sz, vp, vp, vp, vp]
     L.lvkv_sst_read_entries_device.restype = i32
+    L.lvkv_sst_merge_entries_scratch_bytes.argtypes = [sz, u32]
+    L.lvkv_sst_merge_entries_scratch_bytes.restype = sz
+    L.lvkv_sst_merge_entries_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, u32, i32, u32, u64,
+                                                vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, sz,
+                                                vp, vp, vp]
+    L.lvkv_sst_merge_entries_device.restype = i32
     L.lvkv_strerror.argtypes = [i32]
     L.lvkv_strerror.restype = ctypes.c_char_p
     L.lvkv_last_hip_error.argtypes = []
@@ -1144,6 +1150,172 @@ def sst_read_table(file, *, filter_policy: Optional[str] = None, max_ulen: int,
                                                      verify=verify, stream=stream)
     e = sst_read_entries(out, out_off, out_len, skip=rstatus, stream=stream)
     return e[:6] + (table, rstatus, e[8])
+
+
+MERGE_OK, MERGE_UNSORTED, MERGE_BAD_KEY, MERGE_CAPACITY, MERGE_BAD_RUNS = range(5)
+MERGE_MAX_RUNS = 64
+MERGE_COMPACT = 1
+
+
+class SstMergeReport(ctypes.Structure):
+    """lvkv_sst_merge_report (include/lvkv_snappy.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("first_bad_entry", ctypes.c_uint32),
+                ("num_in", ctypes.c_uint32), ("num_out", ctypes.c_uint32),
+                ("num_hidden", ctypes.c_uint32), ("num_obsolete", ctypes.c_uint32),
+                ("max_key_len", ctypes.c_uint32), ("reserved_", ctypes.c_uint32),
+                ("key_bytes", ctypes.c_uint64), ("value_bytes", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.endswith("_")}
+
+
+def _pack_deeper(torch, dev, deeper):
+    """[(smallest, largest) user keys] -> (keys uint8, offsets int64, lengths
+    int32) on the device, range g at 2g and 2g + 1."""
+    flat = [bytes(k) for pair in deeper for k in pair]
+    offs, at = [], 0
+    for k in flat:
+        offs.append(at)
+        at += len(k)
+    keys = torch.tensor(list(b"".join(flat)) or [0], dtype=torch.uint8, device=dev)
+    return (keys, torch.tensor(offs, dtype=torch.int64, device=dev),
+            torch.tensor([len(k) for k in flat], dtype=torch.int32, device=dev))
+
+
+def sst_merge_entries(keys, key_off, key_len, vals, val_off, val_len, run_first, *,
+                      key_format: int = 1, compact: bool = False, smallest_snapshot: int = 0,
+                      deeper=None, max_out: Optional[int] = None, stream=None):
+    """MergingIterator's forward walk over sorted runs of entries, with
+    DoCompactionWork's drops when compact (lvkv_sst_merge_entries_device). The
+    six entry arrays are sst_build_blocks'; they hold the runs laid end to
+    end, run r being entries run_first[r] .. run_first[r + 1] (int64 CUDA
+    tensor of nruns + 1, or a list). deeper: [(smallest, largest)] user keys
+    of the files in levels level + 2 and deeper, as bytes. Returns (out_key_off
+    int64, out_key_len int32, out_val_off int64, out_val_len int32 -- with keys
+    and vals, sst_build_blocks' inputs -- src int32, dropped_src int32, report
+    dict): the survivors in merged order, cut to report['num_out'], each the
+    input entry src[j]; dropped_src the dropped entries' input indices in
+    merged order. report['status'] is MERGE_*, and the arrays are empty unless
+    it is MERGE_OK. The report is the one thing read back."""
+    torch = _torch()
+    n = key_off.numel()
+    dev = keys.device
+    if not (key_len.numel() == val_off.numel() == val_len.numel() == n):
+        raise ValueError("the entry arrays differ in length")
+    if not isinstance(run_first, torch.Tensor):
+        run_first = torch.tensor(list(run_first), dtype=torch.int64, device=dev)
+    nruns = run_first.numel() - 1
+    if max_out is None:
+        max_out = n
+    deeper = list(deeper or [])
+    dkeys, doff, dlen = _pack_deeper(torch, dev, deeper) if deeper else (None, None, None)
+    scratch = torch.empty(int(_lib.lvkv_sst_merge_entries_scratch_bytes(n, max(nruns, 0))),
+                          dtype=torch.uint8, device=dev)
+    slots = max(1, max_out)
+    out_key_off = torch.empty(slots, dtype=torch.int64, device=dev)
+    out_key_len = torch.empty(slots, dtype=torch.int32, device=dev)
+    out_val_off = torch.empty(slots, dtype=torch.int64, device=dev)
+    out_val_len = torch.empty(slots, dtype=torch.int32, device=dev)
+    src = torch.empty(slots, dtype=torch.int32, device=dev)
+    dropped = torch.empty(max(1, n), dtype=torch.int32, device=dev)
+    rep = torch.zeros(ctypes.sizeof(SstMergeReport), dtype=torch.uint8, device=dev)
+    b8 = (torch.uint8, torch.int8)
+    with torch.cuda.device(dev):
+        rc = _lib.lvkv_sst_merge_entries_device(
+            _dev_ptr(keys, "keys", b8) if n else None,
+            _dev_ptr(key_off, "key_off", (torch.int64,)) if n else None,
+            _dev_ptr(key_len, "key_len", (torch.int32,)) if n else None,
+            _dev_ptr(vals, "vals", b8) if n else None,
+            _dev_ptr(val_off, "val_off", (torch.int64,)) if n else None,
+            _dev_ptr(val_len, "val_len", (torch.int32,)) if n else None, n,
+            _dev_ptr(run_first, "run_first", (torch.int64,)), max(nruns, 0), int(key_format),
+            MERGE_COMPACT if compact else 0, int(smallest_snapshot),
+            _dev_ptr(dkeys, "deeper keys") if deeper else None,
+            _dev_ptr(doff, "deeper offsets") if deeper else None,
+            _dev_ptr(dlen, "deeper lengths") if deeper else None, len(deeper),
+            _dev_ptr(scratch, "scratch", b8), scratch.numel(),
+            _dev_ptr(out_key_off, "out_key_off"), _dev_ptr(out_key_len, "out_key_len"),
+            _dev_ptr(out_val_off, "out_val_off"), _dev_ptr(out_val_len, "out_val_len"),
+            _dev_ptr(src, "src"), int(max_out), _dev_ptr(dropped, "dropped_src"),
+            _dev_ptr(rep, "report"), _stream_handle(stream, dev))
+    _check("lvkv_sst_merge_entries_device", rc)
+    if stream is not None:
+        stream.synchronize()
+    report = SstMergeReport.from_buffer_copy(bytes(rep.cpu().numpy())).as_dict()
+    ok = report["status"] == MERGE_OK
+    no = report["num_out"] if ok else 0
+    nd = report["num_hidden"] + report["num_obsolete"] if ok else 0
+    return (out_key_off[:no], out_key_len[:no], out_val_off[:no], out_val_len[:no], src[:no],
+            dropped[:nd], report)
+
+
+def sst_compact_tables(files, *, smallest_snapshot: int, deeper=None,
+                       filter_policy: Optional[str] = None, max_ulen: int, verify: bool = True,
+                       block_size: int = 4096, restart_interval: int = 16, compression: int = 1,
+                       zstd_level: int = 1, filter_bits_per_key: int = 10, file=None,
+                       file_capacity: Optional[int] = None, stream=None):
+    """Table images in device memory -> one compacted table image in device
+    memory, no entry crossing to the host: sst_read_table's steps on each image (a run
+    an image, in the order given: for equal keys the earlier image's entry
+    comes first), the key and value buffers laid end to end with their offsets
+    shifted, sst_merge_entries(compact=True) with smallest_snapshot and the
+    deeper levels' ranges, then sst_build_table over the survivors. The tables
+    hold internal keys. Returns sst_build_table's tuple and the merge report:
+    (file, handle offsets, handle sizes, types, status, table report, build
+    report, merge report); the first seven are None when the merge's status is
+    not MERGE_OK. An image that does not open, or a block of one that does not
+    read or walk, raises ValueError: a compaction does not go on past a bad
+    input. The reports of the calls are read on the host in between.
+
+    One output table: cutting the output into several files (ShouldStopBefore,
+    MaxOutputFileSize) and rewriting the vTable indices of the values are the
+    caller's."""
+    torch = _torch()
+    parts, run_first = [], [0]
+    key_base = val_base = 0
+    dev = None
+    for i, img in enumerate(files):
+        dev = img.device
+        # sst_read_table's three steps, with the table nothing was added to
+        # taken for what it is: its index block is one restart point and no
+        # entry (8 bytes), which the verifier, counting restart points, lists
+        # as one handle that does not decode
+        table, off, size, _, _ = sst_verify_table(img, filter_policy=filter_policy, stream=stream)
+        if table["status"] != 0:
+            raise ValueError(f"input table {i} does not open: status {table['status']}")
+        nd = 0 if table["ndata"] == 1 and table["index_size"] == 8 else table["ndata"]
+        out, out_off, out_len, rstatus = sst_read_blocks(img, off[:nd], size[:nd],
+                                                         max_ulen=max_ulen, verify=verify,
+                                                         stream=stream)
+        t = sst_read_entries(out, out_off, out_len, skip=rstatus, stream=stream)
+        erep = t[8]
+        if erep["status"] != 0 or erep["nbad"] != 0 or bool(rstatus.any().item()):
+            raise ValueError(f"input table {i} has a block that does not read: block status "
+                             f"{rstatus.tolist()}, entries report {erep}")
+        keys, key_off, key_len, vals, val_off, val_len = t[:6]
+        kb = (erep["key_bytes"] + 7) & ~7  # the next run's keys stay 8 bytes apart
+        parts.append((keys[:kb] if keys.numel() >= kb else
+                      torch.cat([keys, keys.new_zeros(kb - keys.numel())]),
+                      key_off + key_base, key_len, vals, val_off + val_base, val_len))
+        key_base += kb
+        val_base += vals.numel()
+        run_first.append(run_first[-1] + key_off.numel())
+    if not parts:
+        raise ValueError("no input tables")
+    keys, key_off, key_len, vals, val_off, val_len = (torch.cat([p[k] for p in parts])
+                                                      for k in range(6))
+    m = sst_merge_entries(keys, key_off, key_len, vals, val_off, val_len,
+                          torch.tensor(run_first, dtype=torch.int64, device=dev), key_format=1,
+                          compact=True, smallest_snapshot=smallest_snapshot, deeper=deeper,
+                          stream=stream)
+    if m[6]["status"] != MERGE_OK:
+        return (None,) * 7 + (m[6],)
+    built = sst_build_table(keys, m[0], m[1], vals, m[2], m[3], block_size=block_size,
+                            restart_interval=restart_interval, key_format=1,
+                            compression=compression, zstd_level=zstd_level,
+                            filter_bits_per_key=filter_bits_per_key, file=file,
+                            file_capacity=file_capacity, stream=stream)
+    return built + (m[6],)
 
 
 class LogReport(ctypes.Structure):

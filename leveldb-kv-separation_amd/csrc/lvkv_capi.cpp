@@ -1158,6 +1158,72 @@ int lvkv_sst_read_entries_device(const void* d_raw, const uint64_t* d_raw_off,
   return e == hipSuccess ? LVKV_OK : hip_fail(e);
 }
 
+size_t lvkv_sst_merge_entries_scratch_bytes(size_t nentries, uint32_t nruns) {
+  (void)nruns;  // (the arrays are per entry whatever the runs are)
+  return sst_merge_scratch_bytes(nentries);
+}
+
+int lvkv_sst_merge_entries_device(const void* d_keys, const uint64_t* d_key_off,
+                                  const uint32_t* d_key_len, const void* d_vals,
+                                  const uint64_t* d_val_off, const uint32_t* d_val_len,
+                                  size_t nentries, const uint64_t* d_run_first, uint32_t nruns,
+                                  int key_format, uint32_t flags, uint64_t smallest_snapshot,
+                                  const void* d_deeper_keys, const uint64_t* d_deeper_off,
+                                  const uint32_t* d_deeper_len, size_t n_deeper, void* d_scratch,
+                                  size_t scratch_bytes, uint64_t* d_out_key_off,
+                                  uint32_t* d_out_key_len, uint64_t* d_out_val_off,
+                                  uint32_t* d_out_val_len, uint32_t* d_out_src, size_t max_out,
+                                  uint32_t* d_dropped_src, lvkv_sst_merge_report* d_report,
+                                  void* stream) {
+  SstMergeArgs a{};
+  a.report = d_report;
+  if (nentries == 0) {
+    if (!d_report) return LVKV_OK;
+    int rc = LVKV_OK;
+    if (current_ctx(&rc) == nullptr) return rc;
+    const hipError_t e = launch_sst_merge(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? LVKV_OK : hip_fail(e);
+  }
+  if (!d_keys || !d_key_off || !d_key_len || !d_vals || !d_val_off || !d_val_len ||
+      !d_run_first || !d_scratch || !d_out_key_off || !d_out_key_len || !d_out_val_off ||
+      !d_out_val_len || !d_out_src || !d_report)
+    return LVKV_ERR_INVALID;
+  if (n_deeper != 0 && (!d_deeper_keys || !d_deeper_off || !d_deeper_len))
+    return LVKV_ERR_INVALID;
+  if (nruns < 1 || nruns > LVKV_MERGE_MAX_RUNS || key_format < 0 || key_format > 1 ||
+      (flags & ~LVKV_MERGE_COMPACT) != 0 || ((flags & LVKV_MERGE_COMPACT) && key_format == 0) ||
+      nentries >= (uint64_t{1} << 31) || n_deeper >= (uint64_t{1} << 31) ||
+      scratch_bytes < lvkv_sst_merge_entries_scratch_bytes(nentries, nruns))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  a.keys = static_cast<const uint8_t*>(d_keys);
+  a.key_off = d_key_off;
+  a.key_len = d_key_len;
+  a.val_off = d_val_off;
+  a.val_len = d_val_len;
+  a.run_first = d_run_first;
+  a.n = static_cast<uint32_t>(nentries);
+  a.nruns = nruns;
+  a.key_format = static_cast<uint32_t>(key_format);
+  a.compact = (flags & LVKV_MERGE_COMPACT) ? 1u : 0u;
+  a.smallest_snapshot = smallest_snapshot;
+  a.deeper_keys = static_cast<const uint8_t*>(d_deeper_keys);
+  a.deeper_off = d_deeper_off;
+  a.deeper_len = d_deeper_len;
+  a.n_deeper = static_cast<uint32_t>(n_deeper);
+  a.scratch = static_cast<uint8_t*>(d_scratch);
+  a.out_key_off = d_out_key_off;
+  a.out_key_len = d_out_key_len;
+  a.out_val_off = d_out_val_off;
+  a.out_val_len = d_out_val_len;
+  a.out_src = d_out_src;
+  a.max_out = max_out;
+  a.dropped_src = d_dropped_src;
+  const hipError_t e = launch_sst_merge(a, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
 int lvkv_sst_write_blocks_device(const void* d_raw, const uint64_t* d_raw_off,
                                  const uint32_t* d_raw_len, size_t nblocks, int compression,
                                  uint32_t max_len, void* d_scratch, void* d_file,

@@ -306,6 +306,37 @@ struct SstEntriesArgs {
 };
 hipError_t launch_sst_entries(const SstEntriesArgs& a, hipStream_t stream);
 
+// ---- MergingIterator and compaction's drops on the device (lvkv_sst_merge.hip) --
+
+// lvkv_sst_merge_entries_scratch_bytes: the call's arrays and alignment slack
+// (the same for every run count).
+size_t sst_merge_scratch_bytes(size_t nentries);
+struct SstMergeArgs {
+  const uint8_t* keys;
+  const uint64_t* key_off;
+  const uint32_t* key_len;
+  const uint64_t* val_off;
+  const uint32_t* val_len;
+  const uint64_t* run_first;  // nruns + 1
+  uint32_t n, nruns, key_format;
+  uint32_t compact;  // 1: LVKV_MERGE_COMPACT
+  uint64_t smallest_snapshot;
+  const uint8_t* deeper_keys;
+  const uint64_t* deeper_off;  // 2 * n_deeper
+  const uint32_t* deeper_len;
+  uint32_t n_deeper;
+  uint8_t* scratch;  // the caller's, sst_merge_scratch_bytes long
+  uint64_t* out_key_off;
+  uint32_t* out_key_len;
+  uint64_t* out_val_off;
+  uint32_t* out_val_len;
+  uint32_t* out_src;
+  uint64_t max_out;
+  uint32_t* dropped_src;  // may be null
+  lvkv_sst_merge_report* report;
+};
+hipError_t launch_sst_merge(const SstMergeArgs& a, hipStream_t stream);
+
 #ifdef LVKV_PROBE_BUILD
 // Probe builds (tools/probe/liblvkv_probe.so): timestamp buffers and knobs
 // set through lvkv_debug_*, the schedule-variant and read-bandwidth launchers.
