@@ -505,6 +505,154 @@ int lvkv_sst_merge_entries_device(
     uint32_t* d_dropped_src /* nentries, may be null */,
     lvkv_sst_merge_report* d_report, void* stream);
 
+/* ---- point lookups: Table::InternalGet for a batch of keys ---- */
+
+/* per query, lvkv_sst_get_locate_device (d_q_status) */
+#define LVKV_GET_BLOCK 0          /* read this block and seek in it */
+#define LVKV_GET_PAST_END 1       /* !iiter->Valid(), status OK: no block can hold the key */
+#define LVKV_GET_FILTERED 2       /* the filter said no */
+#define LVKV_GET_INDEX_CORRUPT 3  /* "bad entry in block" from the index iterator, or an index
+                                     block no iterator can be made for */
+#define LVKV_GET_BAD_HANDLE 4     /* the index entry's value is no BlockHandle (or its size does
+                                     not fit 32 bits); the filter is not asked */
+#define LVKV_GET_BAD_KEY 5        /* key_format 1 and a query under 8 bytes */
+#define LVKV_GET_NSTATUS 6
+/* per query, lvkv_sst_get_seek_device (d_state) */
+#define LVKV_GET_STATE_NOT_FOUND 0
+#define LVKV_GET_STATE_FOUND 1
+#define LVKV_GET_STATE_DELETED 2
+#define LVKV_GET_STATE_CORRUPT_KEY 3  /* ParseInternalKey fails on the entry (kCorrupt) */
+#define LVKV_GET_STATE_BAD_BLOCK 4    /* "bad block contents": under 4 bytes, or the restart
+                                         count too large */
+#define LVKV_GET_STATE_BAD_ENTRY 5    /* "bad entry in block" during the seek */
+#define LVKV_GET_STATE_UNREADABLE 6   /* d_skip says so, or d_q_slot is at or past nblocks */
+#define LVKV_GET_STATE_BAD_KEY 7      /* key_format 1 and a query under 8 bytes (before the slot is
+                                         looked at) */
+#define LVKV_GET_NSTATE 8
+
+typedef struct lvkv_sst_get_locate_report {
+  uint32_t nqueries;
+  uint32_t count[LVKV_GET_NSTATUS];  /* queries with each LVKV_GET_* status */
+  uint32_t reserved_;                /* 0 */
+} lvkv_sst_get_locate_report;
+
+typedef struct lvkv_sst_get_seek_report {
+  uint32_t nqueries;
+  uint32_t count[LVKV_GET_NSTATE];   /* queries with each LVKV_GET_STATE_* */
+} lvkv_sst_get_seek_report;
+
+/* The scratch of lvkv_sst_get_locate_device for nqueries queries on an index
+ * block of index_len bytes, and of lvkv_sst_get_seek_device for nqueries
+ * queries (the counts a workgroup of queries leaves for the report); neither
+ * decreases when an argument grows. */
+size_t lvkv_sst_get_locate_scratch_bytes(uint32_t index_len, size_t nqueries);
+size_t lvkv_sst_get_seek_scratch_bytes(size_t nqueries);
+
+/*
+ * The first half of Table::InternalGet (table/table.cc:214-227) for nqueries
+ * keys, in one stream-ordered call: iiter->Seek(k) on the decoded index block
+ * d_index[0, index_len), BlockHandle::DecodeFrom on the entry it stops at, and
+ * filter->KeyMayMatch(handle.offset(), k) on the decoded filter block
+ * d_filter[0, filter_len) (d_filter NULL: no filter policy, nothing is
+ * filtered). Query q is d_qkeys[d_qkey_off[q], + d_qkey_len[q]), the build
+ * call's key layout: key_format 1, internal keys as LookupKey::internal_key()
+ * makes them (user key, then (sequence << 8) | kValueTypeForSeek as 8
+ * little-endian bytes) under InternalKeyComparator; 0, plain keys under
+ * BytewiseComparator.
+ *
+ * Seek is Block::Iter::Seek on a fresh iterator (table/block.cc:165-228), step
+ * for step: the bisection over the restart array as it stands with mid =
+ * (left + right + 1) / 2, a restart entry that does not decode (an offset
+ * within 3 bytes of the restart array or past it included) or has shared != 0
+ * being corrupt; then SeekToRestartPoint(left) and ParseNextKey until the key
+ * is not below the query, where an offset at or past the restart array is a
+ * clean end and shared above the previous key's length is corrupt. A block
+ * under 4 bytes or with too large a restart count is INDEX_CORRUPT, one with
+ * no restarts PAST_END (NewEmptyIterator).
+ *
+ * The filter is FilterBlockReader as written (table/filter_block.cc:77-104):
+ * under 5 bytes or last_word > n - 5, everything may match; else index =
+ * offset >> base_lg, an empty filter (start == limit) says no, any other
+ * inconsistency yes; BloomFilterPolicy::KeyMayMatch (util/bloom.cc:56-80) on
+ * the user key under key_format 1 (InternalFilterPolicy), on the whole key
+ * under 0: a filter under 2 bytes says no, k > 30 yes. A base_lg of 64 or
+ * more (an undefined shift there) gives index 0.
+ *
+ * Per query: d_q_status[q] = LVKV_GET_*; d_q_block[q] = the number of entries
+ * SeekToFirst + Next hand out before the entry the seek stopped at
+ * (0xFFFFFFFF where that walk does not come by it, as with a lying restart
+ * array, and whenever the seek stopped at none); d_q_handle_off[q] and
+ * d_q_handle_size[q] = the BlockHandle with BLOCK and FILTERED, else 0.
+ *
+ * Differences from the reference, both on purpose. Under key_format 1
+ * InternalKeyComparator reads 8 bytes before the end of any key it is given:
+ * here a query under 8 bytes is BAD_KEY, and a restart key or a walked key
+ * under 8 bytes is INDEX_CORRUPT. DecodeEntry's non_shared + value_length is
+ * taken in 64 bits, as lvkv_sst_read_entries_device does.
+ *
+ * No synchronisation, no copy to the host: d_report (device memory) holds
+ * the count of each status. Nothing is written at or past slot nqueries.
+ *
+ * nqueries == 0, before every other check: LVKV_OK, and an empty report where
+ * d_report is not null (every pointer may be null). LVKV_ERR_INVALID, before
+ * any launch: a null pointer other than d_filter, nqueries >= 2^31,
+ * key_format outside 0..1, scratch_bytes under the sizing function's value.
+ */
+int lvkv_sst_get_locate_device(
+    const void* d_index, uint32_t index_len,
+    const void* d_filter /* may be null */, uint32_t filter_len,
+    const void* d_qkeys, const uint64_t* d_qkey_off, const uint32_t* d_qkey_len, size_t nqueries,
+    int key_format, void* d_scratch, size_t scratch_bytes,
+    uint32_t* d_q_block, uint64_t* d_q_handle_off, uint32_t* d_q_handle_size, uint8_t* d_q_status,
+    lvkv_sst_get_locate_report* d_report, void* stream);
+
+/*
+ * The second half (table/table.cc:228-235): block_iter->Seek(k) in one decoded
+ * data block a query, and SaveValue (db/version_set.cc:263-276) on the entry
+ * it stops at. The blocks are d_raw[d_raw_off[b], + d_raw_len[b]) for b <
+ * nblocks -- lvkv_sst_read_blocks_device's d_out, d_out_off and d_out_len;
+ * d_skip (may be null) is that call's d_status, a non-zero byte meaning the
+ * block could not be read. d_q_slot[q] picks query q's block: the caller's
+ * mapping from the locate call's d_q_block to where it decoded that block, so
+ * that only the blocks a batch touches need decoding. 0xFFFFFFFF: no block,
+ * NOT_FOUND; any other slot at or past nblocks: UNREADABLE, and no block is
+ * read for it. The queries and key_format are the locate call's.
+ *
+ * The seek is the locate call's, and never moves on to the next block: a
+ * walk that reaches the restart array is NOT_FOUND, as in InternalGet; so is
+ * a restart count of 0. Per query: d_hit_off[q] = the offset in its block of
+ * the entry the seek stopped at, 0xFFFFFFFF when it stopped at none;
+ * d_val_off[q] (into d_raw) and d_val_len[q] = that entry's value, 0 when
+ * none -- values are not copied, and a value that is a kVTableIndex record
+ * stays bytes for the caller to resolve; d_tag[q] = the last 8 bytes of the
+ * entry's key as a little-endian u64 under key_format 1, else 0; d_state[q] =
+ * LVKV_GET_STATE_*. Under key_format 1, FOUND and DELETED are SaveValue's:
+ * the entry's key parses (type byte <= 1, else CORRUPT_KEY), its user key
+ * equals the query's byte-wise, and the type decides; an entry with another
+ * user key leaves NOT_FOUND with d_hit_off, the value and the tag describing
+ * it. Under key_format 0, FOUND: the entry's key equals the query.
+ *
+ * Keys of any length are compared exactly. The same two differences from the
+ * reference: a query under 8 bytes (key_format 1) is BAD_KEY, before its slot
+ * is looked at; a restart key or walked key under 8 bytes is BAD_ENTRY.
+ *
+ * No synchronisation, no copy to the host: d_report (device memory) holds
+ * the count of each state. Nothing is written at or past slot nqueries.
+ *
+ * nqueries == 0, before every other check: LVKV_OK, and an empty report where
+ * d_report is not null (every pointer may be null). LVKV_ERR_INVALID, before
+ * any launch: a null pointer other than d_skip, nqueries or nblocks >= 2^31,
+ * key_format outside 0..1, scratch_bytes under the sizing function's value.
+ */
+int lvkv_sst_get_seek_device(
+    const void* d_raw, const uint64_t* d_raw_off, const uint32_t* d_raw_len,
+    const uint8_t* d_skip /* may be null */, size_t nblocks,
+    const void* d_qkeys, const uint64_t* d_qkey_off, const uint32_t* d_qkey_len,
+    const uint32_t* d_q_slot, size_t nqueries, int key_format,
+    void* d_scratch, size_t scratch_bytes,
+    uint32_t* d_hit_off, uint64_t* d_val_off, uint32_t* d_val_len, uint64_t* d_tag,
+    uint8_t* d_state, lvkv_sst_get_seek_report* d_report, void* stream);
+
 /* ReadBlock verdicts */
 #define LVKV_READ_OK 0
 #define LVKV_READ_CHECKSUM 1        /* "block checksum mismatch" (table/format.cc:95-98) */

@@ -200,6 +200,16 @@ def _load() -> ctypes.CDLL:
                                                 vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, sz,
                                                 vp, vp, vp]
     L.lvkv_sst_merge_entries_device.restype = i32
+    L.lvkv_sst_get_locate_scratch_bytes.argtypes = [u32, sz]
+    L.lvkv_sst_get_locate_scratch_bytes.restype = sz
+    L.lvkv_sst_get_seek_scratch_bytes.argtypes = [sz]
+    L.lvkv_sst_get_seek_scratch_bytes.restype = sz
+    L.lvkv_sst_get_locate_device.argtypes = [vp, u32, vp, u32, vp, vp, vp, sz, i32, vp, sz, vp, vp,
+                                             vp, vp, vp, vp]
+    L.lvkv_sst_get_locate_device.restype = i32
+    L.lvkv_sst_get_seek_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, sz, i32, vp, sz, vp,
+                                           vp, vp, vp, vp, vp, vp]
+    L.lvkv_sst_get_seek_device.restype = i32
     L.lvkv_strerror.argtypes = [i32]
     L.lvkv_strerror.restype = ctypes.c_char_p
     L.lvkv_last_hip_error.argtypes = []
@@ -1247,6 +1257,262 @@ def sst_merge_entries(keys, key_off, key_len, vals, val_off, val_len, run_first,
     nd = report["num_hidden"] + report["num_obsolete"] if ok else 0
     return (out_key_off[:no], out_key_len[:no], out_val_off[:no], out_val_len[:no], src[:no],
             dropped[:nd], report)
+
+
+GET_BLOCK, GET_PAST_END, GET_FILTERED, GET_INDEX_CORRUPT, GET_BAD_HANDLE, GET_BAD_KEY = range(6)
+(GET_STATE_NOT_FOUND, GET_STATE_FOUND, GET_STATE_DELETED, GET_STATE_CORRUPT_KEY,
+ GET_STATE_BAD_BLOCK, GET_STATE_BAD_ENTRY, GET_STATE_UNREADABLE, GET_STATE_BAD_KEY) = range(8)
+GET_NO_SLOT = -1  # d_q_slot 0xFFFFFFFF as int32
+
+
+class SstGetLocateReport(ctypes.Structure):
+    """lvkv_sst_get_locate_report (include/lvkv_snappy.h)."""
+    _fields_ = [("nqueries", ctypes.c_uint32), ("count", ctypes.c_uint32 * 6),
+                ("reserved_", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {"nqueries": self.nqueries, "count": list(self.count)}
+
+
+class SstGetSeekReport(ctypes.Structure):
+    """lvkv_sst_get_seek_report (include/lvkv_snappy.h)."""
+    _fields_ = [("nqueries", ctypes.c_uint32), ("count", ctypes.c_uint32 * 8)]
+
+    def as_dict(self) -> dict:
+        return {"nqueries": self.nqueries, "count": list(self.count)}
+
+
+def sst_get_locate(index, filter, qkeys, qkey_off, qkey_len, *, key_format: int = 1,
+                   stream=None):
+    """The index seek and the filter of Table::InternalGet for a batch of keys
+    (lvkv_sst_get_locate_device). index: the decoded index block (uint8 CUDA
+    tensor, all of it); filter: the decoded filter block, or None for no
+    policy; query q is qkeys[qkey_off[q] : qkey_off[q] + qkey_len[q]]
+    (key_format 1: LookupKey::internal_key(), 0: plain bytes). Returns (block
+    int32 -- the index entry's ordinal, -1 for none --, handle offsets int64,
+    handle sizes int32, status uint8 GET_*, report dict). The report is the
+    one thing read back."""
+    torch = _torch()
+    n = qkey_off.numel()
+    dev = index.device
+    if qkey_len.numel() != n:
+        raise ValueError("the query arrays differ in length")
+    scratch = torch.empty(int(_lib.lvkv_sst_get_locate_scratch_bytes(index.numel(), n)),
+                          dtype=torch.uint8, device=dev)
+    slots = max(1, n)
+    block = torch.empty(slots, dtype=torch.int32, device=dev)
+    hoff = torch.empty(slots, dtype=torch.int64, device=dev)
+    hsize = torch.empty(slots, dtype=torch.int32, device=dev)
+    status = torch.empty(slots, dtype=torch.uint8, device=dev)
+    rep = torch.zeros(ctypes.sizeof(SstGetLocateReport), dtype=torch.uint8, device=dev)
+    b8 = (torch.uint8, torch.int8)
+    with torch.cuda.device(dev):
+        rc = _lib.lvkv_sst_get_locate_device(
+            _dev_ptr(index, "index", b8), index.numel(),
+            _dev_ptr(filter, "filter", b8) if filter is not None else None,
+            filter.numel() if filter is not None else 0,
+            _dev_ptr(qkeys, "qkeys", b8) if n else None,
+            _dev_ptr(qkey_off, "qkey_off", (torch.int64,)) if n else None,
+            _dev_ptr(qkey_len, "qkey_len", (torch.int32,)) if n else None, n, int(key_format),
+            _dev_ptr(scratch, "scratch", b8), scratch.numel(), _dev_ptr(block, "block"),
+            _dev_ptr(hoff, "handle_off"), _dev_ptr(hsize, "handle_size"),
+            _dev_ptr(status, "status"), _dev_ptr(rep, "report"), _stream_handle(stream, dev))
+    _check("lvkv_sst_get_locate_device", rc)
+    if stream is not None:
+        stream.synchronize()
+    report = SstGetLocateReport.from_buffer_copy(bytes(rep.cpu().numpy())).as_dict()
+    return block[:n], hoff[:n], hsize[:n], status[:n], report
+
+
+def sst_get_seek(raw, raw_off, raw_len, qkeys, qkey_off, qkey_len, q_slot, *, skip=None,
+                 key_format: int = 1, stream=None):
+    """The data block seek and SaveValue of Table::InternalGet for a batch of
+    keys (lvkv_sst_get_seek_device). The blocks are sst_read_blocks' out,
+    out_offsets and lengths (skip: its status); q_slot[q] (int32) is the block
+    query q seeks in, GET_NO_SLOT for none. Returns (state uint8 GET_STATE_*,
+    hit_off int32 -- -1 for none --, val_off int64 into raw, val_len int32,
+    tag int64, report dict). The report is the one thing read back."""
+    torch = _torch()
+    n = qkey_off.numel()
+    nb = raw_off.numel()
+    dev = qkeys.device
+    if qkey_len.numel() != n or q_slot.numel() != n:
+        raise ValueError("the query arrays differ in length")
+    if raw_len.numel() != nb or (skip is not None and skip.numel() != nb):
+        raise ValueError("the block arrays differ in length")
+    if nb == 0:  # (no block to seek in: the pointers still have to be some)
+        raw = torch.zeros(8, dtype=torch.uint8, device=dev)
+        raw_off = torch.zeros(1, dtype=torch.int64, device=dev)
+        raw_len = torch.zeros(1, dtype=torch.int32, device=dev)
+        skip = None
+    slots = max(1, n)
+    scratch = torch.empty(int(_lib.lvkv_sst_get_seek_scratch_bytes(n)), dtype=torch.uint8,
+                          device=dev)
+    state = torch.empty(slots, dtype=torch.uint8, device=dev)
+    hit = torch.empty(slots, dtype=torch.int32, device=dev)
+    voff = torch.empty(slots, dtype=torch.int64, device=dev)
+    vlen = torch.empty(slots, dtype=torch.int32, device=dev)
+    tag = torch.empty(slots, dtype=torch.int64, device=dev)
+    rep = torch.zeros(ctypes.sizeof(SstGetSeekReport), dtype=torch.uint8, device=dev)
+    b8 = (torch.uint8, torch.int8)
+    with torch.cuda.device(dev):
+        rc = _lib.lvkv_sst_get_seek_device(
+            _dev_ptr(raw, "raw", b8), _dev_ptr(raw_off, "raw_off", (torch.int64,)),
+            _dev_ptr(raw_len, "raw_len", (torch.int32,)),
+            _dev_ptr(skip, "skip", (torch.uint8,)) if skip is not None else None, nb,
+            _dev_ptr(qkeys, "qkeys", b8) if n else None,
+            _dev_ptr(qkey_off, "qkey_off", (torch.int64,)) if n else None,
+            _dev_ptr(qkey_len, "qkey_len", (torch.int32,)) if n else None,
+            _dev_ptr(q_slot, "q_slot", (torch.int32,)) if n else None, n, int(key_format),
+            _dev_ptr(scratch, "scratch", b8), scratch.numel(), _dev_ptr(hit, "hit_off"), _dev_ptr(voff, "val_off"), _dev_ptr(vlen, "val_len"),
+            _dev_ptr(tag, "tag"), _dev_ptr(state, "state"), _dev_ptr(rep, "report"),
+            _stream_handle(stream, dev))
+    _check("lvkv_sst_get_seek_device", rc)
+    if stream is not None:
+        stream.synchronize()
+    report = SstGetSeekReport.from_buffer_copy(bytes(rep.cpu().numpy())).as_dict()
+    return state[:n], hit[:n], voff[:n], vlen[:n], tag[:n], report
+
+
+def _read_one_block(file, off: int, size: int, *, max_ulen: int, verify: bool, stream):
+    """One block of the image, whatever its decoded length: a first guess of
+    the room, once more with what ReadBlock says it needs. Returns (contents
+    uint8 or None, READ_* status)."""
+    torch = _torch()
+    dev = file.device
+    if off + size + 5 > file.numel():
+        return None, READ_BAD_TYPE
+    cap = max(4 * size, 4096)
+    for _ in range(2):
+        out, _, out_len, status = sst_read_blocks(
+            file, torch.tensor([off], dtype=torch.int64, device=dev),
+            torch.tensor([size], dtype=torch.int32, device=dev), max_ulen=max_ulen, verify=verify,
+            out=torch.empty(cap, dtype=torch.uint8, device=dev),
+            out_offsets=torch.zeros(1, dtype=torch.int64, device=dev),
+            out_caps=torch.tensor([cap], dtype=torch.int32, device=dev), stream=stream)
+        if stream is not None:
+            stream.synchronize()
+        st, ln = int(status.cpu()[0]), int(out_len.cpu()[0])
+        if st != READ_CAPACITY:
+            break
+        cap = ln
+    return (out[:ln] if st == READ_OK else None), st
+
+
+def _meta_filter_handle(file, table, filter_policy: str, **read):
+    """Table::ReadMeta (table/table.cc:81-105): the handle under the exact key
+    "filter." + policy in the metaindex block, or None -- the lookup is a
+    seek with plain keys in that one block."""
+    torch = _torch()
+    dev = file.device
+    meta, _ = _read_one_block(file, table["meta_offset"], table["meta_size"], **read)
+    if meta is None:
+        return None
+    key = b"filter." + filter_policy.encode()
+    state, _, voff, vlen, _, _ = sst_get_seek(
+        meta, torch.zeros(1, dtype=torch.int64, device=dev),
+        torch.tensor([meta.numel()], dtype=torch.int32, device=dev),
+        torch.tensor(list(key), dtype=torch.uint8, device=dev),
+        torch.zeros(1, dtype=torch.int64, device=dev),
+        torch.tensor([len(key)], dtype=torch.int32, device=dev),
+        torch.zeros(1, dtype=torch.int32, device=dev), key_format=0, stream=read["stream"])
+    if int(state.cpu()[0]) != GET_STATE_FOUND:
+        return None
+    at, n = int(voff.cpu()[0]), int(vlen.cpu()[0])
+    value, out, p = bytes(meta[at:at + n].cpu().numpy()), [], 0
+    for _ in range(2):  # BlockHandle::DecodeFrom
+        v, shift = 0, 0
+        while True:
+            if p >= len(value) or shift > 63:
+                return None
+            b = value[p]
+            p += 1
+            v |= (b & 127) << shift
+            shift += 7
+            if not b & 128:
+                break
+        out.append(v)
+    return out[0], out[1]
+
+
+def sst_get(file, qkeys, qkey_off, qkey_len, *, filter_policy: Optional[str] = None,
+            key_format: int = 1, max_ulen: int, verify: bool = True, stream=None):
+    """Table::InternalGet for a batch of keys on one table image in device
+    memory: sst_verify_table (the footer's handles, the filter's), the index
+    and filter blocks through sst_read_blocks, sst_get_locate, one
+    sst_read_blocks over the distinct data blocks the GET_BLOCK queries name
+    (max_ulen: the longest decoded data block) and sst_get_seek in them. The
+    reports are read on the host between the steps; a batch whose every query
+    is filtered or past the end decodes no data block. Returns a dict: state
+    (uint8 GET_STATE_*), val_off / val_len into `values` (the decoded blocks),
+    tag, hit_off, status (uint8 GET_*: the locate verdicts), block, raw_off /
+    raw_len / read_status (the decoded blocks, one a distinct block), and the
+    reports table, locate, seek. When the table does not open (table['status']
+    != 0) or its index block cannot be read, only the reports are there (index
+    status under 'index_read'). One exception: sst_verify_table stops at a
+    compressed index block (status 6 with a sound checksum); the index is
+    decoded here all the same, and the filter block is then found through the
+    metaindex block. Which table of a version a key is looked up in, and in
+    what order, stays the caller's."""
+    torch = _torch()
+    dev = file.device
+    n = qkey_off.numel()
+    table, off, size, _, vstatus = sst_verify_table(file, filter_policy=filter_policy,
+                                                    stream=stream)
+    res = {"table": table}
+    # (the verifier has no codec for a compressed index block: it reports the
+    # footer's handles and stops; the index is decoded here all the same)
+    packed_index = table["status"] == 6 and table["index_status"] == 6
+    if table["status"] != 0 and not packed_index:
+        return res
+    small = min(max_ulen, SNAPPY_MAX_BLOCK)
+    read = dict(max_ulen=small, verify=verify, stream=stream)
+    index, ist = _read_one_block(file, table["index_offset"], table["index_size"], **read)
+    res["index_read"] = ist
+    if index is None:
+        return res
+    filt = None
+    if filter_policy is not None:
+        # (a filter block that cannot be read is no filter: Table::ReadFilter)
+        nd = table["ndata"]
+        if packed_index:
+            h = _meta_filter_handle(file, table, filter_policy, **read)
+        elif table["has_filter"] and int(vstatus[nd].cpu()) == 0:
+            h = int(off[nd].cpu()), int(size[nd].cpu()) & 0xFFFFFFFF
+        else:
+            h = None
+        if h is not None:
+            filt, _ = _read_one_block(file, h[0], h[1], **read)
+    block, hoff, hsize, status, locate = sst_get_locate(index, filt, qkeys, qkey_off, qkey_len,
+                                                        key_format=key_format, stream=stream)
+    slot = torch.full((n,), GET_NO_SLOT, dtype=torch.int32, device=dev)
+    raw = raw_off = raw_len = rstatus = None
+    if locate["count"][GET_BLOCK] != 0:
+        wanted = status == GET_BLOCK
+        pairs = torch.stack([hoff[wanted], hsize[wanted].to(torch.int64) & 0xFFFFFFFF], dim=1)
+        uniq, inverse = torch.unique(pairs, dim=0, return_inverse=True)
+        # a handle that leaves the image is not read: its queries get a slot past the blocks
+        inside = (uniq[:, 0] >= 0) & (uniq[:, 0] + uniq[:, 1] + 5 <= file.numel())
+        place = torch.cumsum(inside.to(torch.int32), 0, dtype=torch.int32) - 1
+        place = torch.where(inside, place, torch.full_like(place, 0x7FFFFFFF))
+        slot[wanted] = place[inverse]
+        uniq = uniq[inside]
+        if uniq.shape[0] != 0:
+            raw, raw_off, raw_len, rstatus = sst_read_blocks(
+                file, uniq[:, 0].contiguous(), uniq[:, 1].to(torch.int32).contiguous(),
+                max_ulen=max_ulen, verify=verify, stream=stream)
+    if raw is None:
+        raw = torch.zeros(8, dtype=torch.uint8, device=dev)
+        raw_off = torch.zeros(0, dtype=torch.int64, device=dev)
+        raw_len = torch.zeros(0, dtype=torch.int32, device=dev)
+        rstatus = torch.zeros(0, dtype=torch.uint8, device=dev)
+    state, hit, voff, vlen, tag, seek = sst_get_seek(raw, raw_off, raw_len, qkeys, qkey_off,
+                                                     qkey_len, slot, skip=rstatus,
+                                                     key_format=key_format, stream=stream)
+    res.update(state=state, val_off=voff, val_len=vlen, values=raw, tag=tag, hit_off=hit,
+               status=status, block=block, raw_off=raw_off, raw_len=raw_len, read_status=rstatus,
+               locate=locate, seek=seek)
+    return res
 
 
 def sst_compact_tables(files, *, smallest_snapshot: int, deeper=None,

@@ -1224,6 +1224,103 @@ int lvkv_sst_merge_entries_device(const void* d_keys, const uint64_t* d_key_off,
   return e == hipSuccess ? LVKV_OK : hip_fail(e);
 }
 
+size_t lvkv_sst_get_locate_scratch_bytes(uint32_t index_len, size_t nqueries) {
+  return sst_get_locate_scratch_bytes(index_len, nqueries);
+}
+
+size_t lvkv_sst_get_seek_scratch_bytes(size_t nqueries) {
+  return sst_get_seek_scratch_bytes(nqueries);
+}
+
+int lvkv_sst_get_locate_device(const void* d_index, uint32_t index_len, const void* d_filter,
+                               uint32_t filter_len, const void* d_qkeys,
+                               const uint64_t* d_qkey_off, const uint32_t* d_qkey_len,
+                               size_t nqueries, int key_format, void* d_scratch,
+                               size_t scratch_bytes, uint32_t* d_q_block,
+                               uint64_t* d_q_handle_off, uint32_t* d_q_handle_size,
+                               uint8_t* d_q_status, lvkv_sst_get_locate_report* d_report,
+                               void* stream) {
+  SstGetLocateArgs a{};
+  a.report = d_report;
+  if (nqueries == 0) {
+    if (!d_report) return LVKV_OK;
+    int rc = LVKV_OK;
+    if (current_ctx(&rc) == nullptr) return rc;
+    const hipError_t e = launch_sst_get_locate(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? LVKV_OK : hip_fail(e);
+  }
+  if (!d_index || !d_qkeys || !d_qkey_off || !d_qkey_len || !d_scratch || !d_q_block ||
+      !d_q_handle_off || !d_q_handle_size || !d_q_status || !d_report)
+    return LVKV_ERR_INVALID;
+  if (nqueries >= (uint64_t{1} << 31) || key_format < 0 || key_format > 1 ||
+      scratch_bytes < lvkv_sst_get_locate_scratch_bytes(index_len, nqueries))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  a.index = static_cast<const uint8_t*>(d_index);
+  a.index_len = index_len;
+  a.filter = static_cast<const uint8_t*>(d_filter);
+  a.filter_len = filter_len;
+  a.qkeys = static_cast<const uint8_t*>(d_qkeys);
+  a.qkey_off = d_qkey_off;
+  a.qkey_len = d_qkey_len;
+  a.n = static_cast<uint32_t>(nqueries);
+  a.key_format = static_cast<uint32_t>(key_format);
+  a.scratch = static_cast<uint8_t*>(d_scratch);
+  a.q_block = d_q_block;
+  a.q_handle_off = d_q_handle_off;
+  a.q_handle_size = d_q_handle_size;
+  a.q_status = d_q_status;
+  const hipError_t e = launch_sst_get_locate(a, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
+int lvkv_sst_get_seek_device(const void* d_raw, const uint64_t* d_raw_off,
+                             const uint32_t* d_raw_len, const uint8_t* d_skip, size_t nblocks,
+                             const void* d_qkeys, const uint64_t* d_qkey_off,
+                             const uint32_t* d_qkey_len, const uint32_t* d_q_slot,
+                             size_t nqueries, int key_format, void* d_scratch,
+                             size_t scratch_bytes, uint32_t* d_hit_off,
+                             uint64_t* d_val_off, uint32_t* d_val_len, uint64_t* d_tag,
+                             uint8_t* d_state, lvkv_sst_get_seek_report* d_report, void* stream) {
+  SstGetSeekArgs a{};
+  a.report = d_report;
+  if (nqueries == 0) {
+    if (!d_report) return LVKV_OK;
+    int rc = LVKV_OK;
+    if (current_ctx(&rc) == nullptr) return rc;
+    const hipError_t e = launch_sst_get_seek(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? LVKV_OK : hip_fail(e);
+  }
+  if (!d_raw || !d_raw_off || !d_raw_len || !d_qkeys || !d_qkey_off || !d_qkey_len || !d_q_slot ||
+      !d_scratch || !d_hit_off || !d_val_off || !d_val_len || !d_tag || !d_state || !d_report)
+    return LVKV_ERR_INVALID;
+  if (nqueries >= (uint64_t{1} << 31) || nblocks >= (uint64_t{1} << 31) || key_format < 0 ||
+      key_format > 1 || scratch_bytes < lvkv_sst_get_seek_scratch_bytes(nqueries))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  a.raw = static_cast<const uint8_t*>(d_raw);
+  a.raw_off = d_raw_off;
+  a.raw_len = d_raw_len;
+  a.skip = d_skip;
+  a.nblocks = static_cast<uint32_t>(nblocks);
+  a.qkeys = static_cast<const uint8_t*>(d_qkeys);
+  a.qkey_off = d_qkey_off;
+  a.qkey_len = d_qkey_len;
+  a.q_slot = d_q_slot;
+  a.n = static_cast<uint32_t>(nqueries);
+  a.key_format = static_cast<uint32_t>(key_format);
+  a.scratch = static_cast<uint8_t*>(d_scratch);
+  a.hit_off = d_hit_off;
+  a.val_off = d_val_off;
+  a.val_len = d_val_len;
+  a.tag = d_tag;
+  a.state = d_state;
+  const hipError_t e = launch_sst_get_seek(a, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
 int lvkv_sst_write_blocks_device(const void* d_raw, const uint64_t* d_raw_off,
                                  const uint32_t* d_raw_len, size_t nblocks, int compression,
                                  uint32_t max_len, void* d_scratch, void* d_file,

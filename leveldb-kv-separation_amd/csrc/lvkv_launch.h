@@ -337,6 +337,51 @@ struct SstMergeArgs {
 };
 hipError_t launch_sst_merge(const SstMergeArgs& a, hipStream_t stream);
 
+// ---- Table::InternalGet for a batch of keys on the device (lvkv_sst_get.hip) ----
+
+// lvkv_sst_get_locate_scratch_bytes: two words for every restart the index
+// block can hold, their scan's sums, the counts a workgroup of queries leaves
+// and alignment slack. lvkv_sst_get_seek_scratch_bytes: those counts.
+size_t sst_get_locate_scratch_bytes(uint32_t index_len, size_t nqueries);
+size_t sst_get_seek_scratch_bytes(size_t nqueries);
+struct SstGetLocateArgs {
+  const uint8_t* index;
+  uint32_t index_len;
+  const uint8_t* filter;  // may be null
+  uint32_t filter_len;
+  const uint8_t* qkeys;
+  const uint64_t* qkey_off;
+  const uint32_t* qkey_len;
+  uint32_t n, key_format;
+  uint8_t* scratch;  // the caller's, sst_get_locate_scratch_bytes long
+  uint32_t* q_block;
+  uint64_t* q_handle_off;
+  uint32_t* q_handle_size;
+  uint8_t* q_status;
+  lvkv_sst_get_locate_report* report;
+};
+hipError_t launch_sst_get_locate(const SstGetLocateArgs& a, hipStream_t stream);
+struct SstGetSeekArgs {
+  const uint8_t* raw;
+  const uint64_t* raw_off;
+  const uint32_t* raw_len;
+  const uint8_t* skip;  // may be null
+  uint32_t nblocks;
+  const uint8_t* qkeys;
+  const uint64_t* qkey_off;
+  const uint32_t* qkey_len;
+  const uint32_t* q_slot;
+  uint32_t n, key_format;
+  uint8_t* scratch;  // the caller's, sst_get_seek_scratch_bytes long
+  uint32_t* hit_off;
+  uint64_t* val_off;
+  uint32_t* val_len;
+  uint64_t* tag;
+  uint8_t* state;
+  lvkv_sst_get_seek_report* report;
+};
+hipError_t launch_sst_get_seek(const SstGetSeekArgs& a, hipStream_t stream);
+
 #ifdef LVKV_PROBE_BUILD
 // Probe builds (tools/probe/liblvkv_probe.so): timestamp buffers and knobs
 // set through lvkv_debug_*, the schedule-variant and read-bandwidth launchers.

@@ -4,9 +4,10 @@
 // (util/hash.cc, util/bloom.cc) and the constants of the footer and the filter
 // block (table/format.h, table/filter_block.cc). Used by the table verifier
 // (lvkv_sst_table.hip), the table finisher (lvkv_sst_finish.hip), the block
-// builder (lvkv_sst_build.hip) and the block walker (lvkv_sst_entries.hip,
-// which takes decode_entry but not block_restarts / block_run: Block::Iter's
-// walk accepts blocks those two refuse).
+// builder (lvkv_sst_build.hip), and the block walker (lvkv_sst_entries.hip)
+// and the point lookups (lvkv_sst_get.hip), which take decode_entry but not
+// block_restarts / block_run: Block::Iter's walk and its Seek accept blocks
+// those two refuse.
 #ifndef LVKV_TABLE_FORMAT_H_
 #define LVKV_TABLE_FORMAT_H_
 
