@@ -30,6 +30,10 @@ uint32_t lvkv_debug_extend_portable(uint32_t crc, const uint8_t* data, size_t n)
 int lvkv_debug_set_general_kernel(int cfg);
 int lvkv_debug_set_log_kernel(int cfg);
 int lvkv_debug_set_sst_form(int form);
+/* The tile of the vTable calls' copy kernel (include/lvkv_vtable.h) for the
+ * calls that follow: 16-byte stores a lane, 1, 2, 4 or 8; 0 restores the
+ * production choice. The results do not depend on it (tools/vtable_bench.py). */
+int lvkv_debug_set_vtable_copy_rows(int rows);
 
 /* lvkv_zstd_uncompress_device with the failure site of each stream
  * (d_detail[i]: 0 none, else the decoder's check that failed; tests). */

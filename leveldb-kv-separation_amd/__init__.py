@@ -210,6 +210,26 @@ def _load() -> ctypes.CDLL:
     L.lvkv_sst_get_seek_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, sz, i32, vp, sz, vp,
                                            vp, vp, vp, vp, vp, vp]
     L.lvkv_sst_get_seek_device.restype = i32
+    L.lvkv_debug_set_vtable_copy_rows.argtypes = [i32]
+    L.lvkv_debug_set_vtable_copy_rows.restype = i32
+    L.lvkv_vtable_separate_scratch_bytes.argtypes = [sz]
+    L.lvkv_vtable_separate_scratch_bytes.restype = sz
+    L.lvkv_vtable_separate_vtb_bound.argtypes = [sz, u64, u64]
+    L.lvkv_vtable_separate_vtb_bound.restype = u64
+    L.lvkv_vtable_separate_vals_bound.argtypes = [sz, u64]
+    L.lvkv_vtable_separate_vals_bound.restype = u64
+    L.lvkv_vtable_separate_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, u64, u64, vp, sz, vp, u64,
+                                              vp, u64, vp, vp, vp, vp, vp, vp]
+    L.lvkv_vtable_separate_device.restype = i32
+    L.lvkv_vtable_resolve_scratch_bytes.argtypes = [sz]
+    L.lvkv_vtable_resolve_scratch_bytes.restype = sz
+    L.lvkv_vtable_resolve_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp,
+                                             vp, vp, vp, vp]
+    L.lvkv_vtable_resolve_device.restype = i32
+    L.lvkv_vtable_gather_scratch_bytes.argtypes = [sz]
+    L.lvkv_vtable_gather_scratch_bytes.restype = sz
+    L.lvkv_vtable_gather_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, u64, vp, vp, vp]
+    L.lvkv_vtable_gather_device.restype = i32
     L.lvkv_strerror.argtypes = [i32]
     L.lvkv_strerror.restype = ctypes.c_char_p
     L.lvkv_last_hip_error.argtypes = []
@@ -1512,6 +1532,249 @@ def sst_get(file, qkeys, qkey_off, qkey_len, *, filter_policy: Optional[str] = N
     res.update(state=state, val_off=voff, val_len=vlen, values=raw, tag=tag, hit_off=hit,
                status=status, block=block, raw_off=raw_off, raw_len=raw_len, read_status=rstatus,
                locate=locate, seek=seek)
+    return res
+
+
+# --------------------------------------------------------------------------
+# KV separation: the vTable (include/lvkv_vtable.h)
+
+VTABLE_OK, VTABLE_BAD_KEY, VTABLE_BAD_VALUE, VTABLE_TOO_LARGE, VTABLE_CAPACITY = range(5)
+VTABLE_NO_ENTRY = 0xFFFFFFFF
+(VRES_OK, VRES_SKIPPED, VRES_EMPTY, VRES_BAD_TYPE, VRES_BAD_INDEX, VRES_BAD_HANDLE, VRES_NO_FILE,
+ VRES_PAST_END, VRES_BAD_HEADER, VRES_BAD_RECORD, VRES_TRAILING, VRES_RECORD_OVERRUN) = range(12)
+
+
+class VtableSeparateReport(ctypes.Structure):
+    """lvkv_vtable_separate_report (include/lvkv_vtable.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("first_bad_entry", ctypes.c_uint32),
+                ("records_num", ctypes.c_uint64), ("table_size", ctypes.c_uint64),
+                ("out_val_bytes", ctypes.c_uint64), ("max_out_val_len", ctypes.c_uint32),
+                ("reserved_", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
+class VtableResolveReport(ctypes.Structure):
+    """lvkv_vtable_resolve_report (include/lvkv_vtable.h)."""
+    _fields_ = [("nqueries", ctypes.c_uint32), ("count", ctypes.c_uint32 * 12),
+                ("max_len", ctypes.c_uint32), ("total_len", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {"nqueries": self.nqueries, "count": list(self.count), "max_len": self.max_len,
+                "total_len": self.total_len}
+
+
+class VtableGatherReport(ctypes.Structure):
+    """lvkv_vtable_gather_report (include/lvkv_vtable.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("nvalues", ctypes.c_uint32),
+                ("dst_bytes", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _read_report(cls, rep, stream):
+    if stream is not None:
+        stream.synchronize()
+    return cls.from_buffer_copy(bytes(rep.cpu().numpy())).as_dict()
+
+
+def vtable_separate(keys, key_off, key_len, vals, val_off, val_len, *, kv_sep_size: int = 1000,
+                    file_number: int, vtb=None, out_vals=None, scratch=None, stream=None):
+    """BuildTable's loop (lvkv_vtable_separate_device): every entry whose value
+    has kv_sep_size bytes or more moves into the vTable image `vtb` as a
+    VTableRecord (user key, the value without its first byte) and gets a
+    VTableIndex for a value; the others keep theirs. Entries as for
+    sst_build_blocks, keys internal keys. vtb / out_vals: allocated by the
+    bounds when None. Returns a dict: vtb, out_vals, out_val_off (int64),
+    out_val_len (int32) -- with the key arrays, sst_build_blocks' arguments --,
+    rec_off / rec_size (int64; 0 / 0 for an entry that stays) and report
+    (status VTABLE_*; nothing is written unless it is VTABLE_OK; on
+    VTABLE_CAPACITY table_size and out_val_bytes say what is needed). The
+    report is the one thing read back."""
+    torch = _torch()
+    n = key_off.numel()
+    dev = keys.device
+    if not (key_len.numel() == val_off.numel() == val_len.numel() == n):
+        raise ValueError("the entry arrays differ in length")
+    if vtb is None or out_vals is None:
+        kb = int(key_len.to(torch.int64).sum().item()) if n else 0
+        vb = int((val_len.to(torch.int64) & 0xFFFFFFFF).sum().item()) if n else 0
+        if vtb is None:
+            vtb = torch.empty(max(1, int(_lib.lvkv_vtable_separate_vtb_bound(n, kb, vb))),
+                              dtype=torch.uint8, device=dev)
+        if out_vals is None:
+            out_vals = torch.empty(max(1, int(_lib.lvkv_vtable_separate_vals_bound(n, vb))),
+                                   dtype=torch.uint8, device=dev)
+    if scratch is None:
+        scratch = torch.empty(int(_lib.lvkv_vtable_separate_scratch_bytes(n)), dtype=torch.uint8,
+                              device=dev)
+    slots = max(1, n)
+    ooff = torch.empty(slots, dtype=torch.int64, device=dev)
+    olen = torch.empty(slots, dtype=torch.int32, device=dev)
+    roff = torch.empty(slots, dtype=torch.int64, device=dev)
+    rsize = torch.empty(slots, dtype=torch.int64, device=dev)
+    rep = torch.zeros(ctypes.sizeof(VtableSeparateReport), dtype=torch.uint8, device=dev)
+    b8 = (torch.uint8, torch.int8)
+    with torch.cuda.device(dev):
+        rc = _lib.lvkv_vtable_separate_device(
+            _dev_ptr(keys, "keys", b8) if n else None,
+            _dev_ptr(key_off, "key_off", (torch.int64,)) if n else None,
+            _dev_ptr(key_len, "key_len", (torch.int32,)) if n else None,
+            _dev_ptr(vals, "vals", b8) if n else None,
+            _dev_ptr(val_off, "val_off", (torch.int64,)) if n else None,
+            _dev_ptr(val_len, "val_len", (torch.int32,)) if n else None,
+            n, int(kv_sep_size), int(file_number), _dev_ptr(scratch, "scratch", b8),
+            scratch.numel(), _dev_ptr(vtb, "vtb", b8), vtb.numel(),
+            _dev_ptr(out_vals, "out_vals", b8), out_vals.numel(), _dev_ptr(ooff, "out_val_off"),
+            _dev_ptr(olen, "out_val_len"), _dev_ptr(roff, "rec_off"), _dev_ptr(rsize, "rec_size"),
+            _dev_ptr(rep, "report"), _stream_handle(stream, dev))
+    _check("lvkv_vtable_separate_device", rc)
+    return dict(vtb=vtb, out_vals=out_vals, out_val_off=ooff[:n], out_val_len=olen[:n],
+                rec_off=roff[:n], rec_size=rsize[:n],
+                report=_read_report(VtableSeparateReport, rep, stream))
+
+
+def _pack_vtables(torch, dev, vtables):
+    """{file number: image} or [(file number, image)] -> one buffer and the
+    three file arrays, ascending by number. An 8-byte buffer for no file."""
+    items = sorted(vtables.items() if isinstance(vtables, dict) else vtables, key=lambda kv: kv[0])
+    sizes = [img.numel() for _, img in items]
+    offs = [0]
+    for sz_ in sizes:
+        offs.append(offs[-1] + sz_)
+    vtb = (torch.cat([img for _, img in items]) if len(items) > 1 else
+           items[0][1] if items else torch.zeros(8, dtype=torch.uint8, device=dev))
+    if vtb.numel() == 0:
+        vtb = torch.zeros(8, dtype=torch.uint8, device=dev)
+    def arr(xs):
+        # (file numbers are u64: two's complement into int64)
+        return torch.tensor([x - (1 << 64) if x >= 1 << 63 else x for x in xs] or [0],
+                            dtype=torch.int64, device=dev)[:len(xs)]
+    return vtb, arr(offs[:-1]), arr(sizes), arr([k for k, _ in items])
+
+
+def vtable_resolve(vals, val_off, val_len, vtb, file_off, file_size, file_number, *, state=None,
+                   stream=None):
+    """DecodeValue and VTableReader::Get for a batch of values
+    (lvkv_vtable_resolve_device): value q is vals[val_off[q] : + val_len[q]];
+    the vTable images lie in `vtb` at file_off / file_size under file_number
+    (int64 tensors, ascending by number; empty for none). state: sst_get_seek's
+    -- only GET_STATE_FOUND queries are looked at. Returns (status uint8
+    VRES_*, src uint8 -- 0: vals, 1: vtb --, off int64, len int32, report
+    dict). No value byte is copied; the report is the one thing read back."""
+    torch = _torch()
+    n = val_off.numel()
+    nf = file_number.numel()
+    dev = vals.device
+    if val_len.numel() != n or (state is not None and state.numel() != n):
+        raise ValueError("the query arrays differ in length")
+    if file_off.numel() != nf or file_size.numel() != nf:
+        raise ValueError("the file arrays differ in length")
+    scratch = torch.empty(int(_lib.lvkv_vtable_resolve_scratch_bytes(n)), dtype=torch.uint8,
+                          device=dev)
+    slots = max(1, n)
+    status = torch.empty(slots, dtype=torch.uint8, device=dev)
+    src = torch.empty(slots, dtype=torch.uint8, device=dev)
+    off = torch.empty(slots, dtype=torch.int64, device=dev)
+    ln = torch.empty(slots, dtype=torch.int32, device=dev)
+    rep = torch.zeros(ctypes.sizeof(VtableResolveReport), dtype=torch.uint8, device=dev)
+    b8 = (torch.uint8, torch.int8)
+    i64 = (torch.int64,)
+    with torch.cuda.device(dev):
+        rc = _lib.lvkv_vtable_resolve_device(
+            _dev_ptr(vals, "vals", b8) if n else None,
+            _dev_ptr(val_off, "val_off", i64) if n else None,
+            _dev_ptr(val_len, "val_len", (torch.int32,)) if n else None,
+            _dev_ptr(state, "state", (torch.uint8,)) if state is not None and n else None, n,
+            _dev_ptr(vtb, "vtb", b8) if nf else None,
+            _dev_ptr(file_off, "file_off", i64) if nf else None,
+            _dev_ptr(file_size, "file_size", i64) if nf else None,
+            _dev_ptr(file_number, "file_number", i64) if nf else None, nf,
+            _dev_ptr(scratch, "scratch", b8), scratch.numel(), _dev_ptr(status, "status"),
+            _dev_ptr(src, "src"), _dev_ptr(off, "off"), _dev_ptr(ln, "len"),
+            _dev_ptr(rep, "report"), _stream_handle(stream, dev))
+    _check("lvkv_vtable_resolve_device", rc)
+    return status[:n], src[:n], off[:n], ln[:n], _read_report(VtableResolveReport, rep, stream)
+
+
+def vtable_gather(vals, vtb, status, src, off, ln, *, dst=None, stream=None):
+    """The values vtable_resolve found, end to end (lvkv_vtable_gather_device):
+    query q's is dst[dst_off[q] : dst_off[q + 1]], empty unless its status is
+    VRES_OK. dst: allocated to fit when None (the resolve report's total_len
+    is not needed: the lengths are added up here). Returns (dst, dst_off int64
+    of n + 1, report dict); on VTABLE_CAPACITY nothing is written."""
+    torch = _torch()
+    n = status.numel()
+    dev = vals.device
+    if not (src.numel() == off.numel() == ln.numel() == n):
+        raise ValueError("the query arrays differ in length")
+    if dst is None:
+        need = int(((ln.to(torch.int64) & 0xFFFFFFFF) * (status == VRES_OK)).sum().item()) if n else 0
+        dst = torch.empty(max(1, need), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(int(_lib.lvkv_vtable_gather_scratch_bytes(n)), dtype=torch.uint8,
+                          device=dev)
+    dst_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    rep = torch.zeros(ctypes.sizeof(VtableGatherReport), dtype=torch.uint8, device=dev)
+    b8 = (torch.uint8, torch.int8)
+    with torch.cuda.device(dev):
+        rc = _lib.lvkv_vtable_gather_device(
+            _dev_ptr(vals, "vals", b8) if n else None, _dev_ptr(vtb, "vtb", b8) if n else None,
+            _dev_ptr(status, "status", (torch.uint8,)) if n else None,
+            _dev_ptr(src, "src", (torch.uint8,)) if n else None,
+            _dev_ptr(off, "off", (torch.int64,)) if n else None,
+            _dev_ptr(ln, "len", (torch.int32,)) if n else None, n,
+            _dev_ptr(scratch, "scratch", b8), scratch.numel(), _dev_ptr(dst, "dst", b8),
+            dst.numel(), _dev_ptr(dst_off, "dst_off"), _dev_ptr(rep, "report"),
+            _stream_handle(stream, dev))
+    _check("lvkv_vtable_gather_device", rc)
+    return dst, dst_off, _read_report(VtableGatherReport, rep, stream)
+
+
+def sst_flush_separated(keys, key_off, key_len, vals, val_off, val_len, *,
+                        kv_sep_size: int = 1000, file_number: int, stream=None, **table_options):
+    """BuildTable on the device: vtable_separate, then sst_build_table on the
+    values it left (table_options: sst_build_table's). Returns (table image,
+    vTable image, reports): the images cut to their sizes (the vTable image
+    empty when nothing moved, where the reference removes the file; the table
+    None when a step failed), reports = {'separate', 'build', 'table'}."""
+    sep = vtable_separate(keys, key_off, key_len, vals, val_off, val_len,
+                          kv_sep_size=kv_sep_size, file_number=file_number, stream=stream)
+    reports = {"separate": sep["report"], "build": None, "table": None}
+    if sep["report"]["status"] != VTABLE_OK:
+        return None, None, reports
+    out = sst_build_table(keys, key_off, key_len, sep["out_vals"], sep["out_val_off"],
+                          sep["out_val_len"], key_format=1, stream=stream, **table_options)
+    reports["build"], reports["table"] = out[6], out[5]
+    vtb = sep["vtb"][:sep["report"]["table_size"]]
+    if out[0] is None or out[5]["status"] != 0:
+        return None, vtb, reports
+    return out[0][:out[5]["file_size"]], vtb, reports
+
+
+def sst_get_values(file, vtables, qkeys, qkey_off, qkey_len, *, stream=None, **get_options):
+    """Keys to values through the value log: sst_get on the table image `file`
+    (get_options: sst_get's, key_format 1), vtable_resolve on what it found
+    against `vtables` ({file number: vTable image}), vtable_gather. Returns a
+    dict: values, value_off (int64 of n + 1: query q's value is values[
+    value_off[q] : value_off[q + 1]]), status (uint8 VRES_*; VRES_SKIPPED for a
+    key that is not there), state (sst_get's), and the reports get, resolve,
+    gather. When the table does not open only 'get' is there."""
+    torch = _torch()
+    dev = file.device
+    got = sst_get(file, qkeys, qkey_off, qkey_len, key_format=1, stream=stream, **get_options)
+    res = {"get": got}
+    if "state" not in got:
+        return res
+    vtb, foff, fsize, fnum = _pack_vtables(torch, dev, vtables)
+    status, src, off, ln, rrep = vtable_resolve(got["values"], got["val_off"], got["val_len"], vtb,
+                                                foff, fsize, fnum, state=got["state"],
+                                                stream=stream)
+    values, value_off, grep = vtable_gather(got["values"], vtb, status, src, off, ln,
+                                            stream=stream)
+    res.update(values=values, value_off=value_off, status=status, state=got["state"],
+               resolve=rrep, gather=grep)
     return res
 
 

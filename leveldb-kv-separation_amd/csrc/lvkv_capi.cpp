@@ -1321,6 +1321,160 @@ int lvkv_sst_get_seek_device(const void* d_raw, const uint64_t* d_raw_off,
   return e == hipSuccess ? LVKV_OK : hip_fail(e);
 }
 
+size_t lvkv_vtable_separate_scratch_bytes(size_t nentries) {
+  return vtable_separate_scratch_bytes(nentries);
+}
+
+uint64_t lvkv_vtable_separate_vtb_bound(size_t nentries, uint64_t total_key_bytes,
+                                        uint64_t total_value_bytes) {
+  return total_key_bytes + total_value_bytes + uint64_t{nentries} * LVKV_VTABLE_RECORD_FRAMING;
+}
+
+uint64_t lvkv_vtable_separate_vals_bound(size_t nentries, uint64_t total_value_bytes) {
+  return total_value_bytes + uint64_t{nentries} * LVKV_VTABLE_INDEX_MAX;
+}
+
+int lvkv_vtable_separate_device(const void* d_keys, const uint64_t* d_key_off,
+                                const uint32_t* d_key_len, const void* d_vals,
+                                const uint64_t* d_val_off, const uint32_t* d_val_len,
+                                size_t nentries, uint64_t kv_sep_size, uint64_t file_number,
+                                void* d_scratch, size_t scratch_bytes, void* d_vtb,
+                                uint64_t vtb_capacity, void* d_out_vals,
+                                uint64_t out_val_capacity, uint64_t* d_out_val_off,
+                                uint32_t* d_out_val_len, uint64_t* d_rec_off,
+                                uint64_t* d_rec_size, lvkv_vtable_separate_report* d_report,
+                                void* stream) {
+  VtableSeparateArgs a{};
+  a.report = d_report;
+  if (nentries == 0) {
+    if (!d_report) return LVKV_OK;
+    int rc = LVKV_OK;
+    if (current_ctx(&rc) == nullptr) return rc;
+    const hipError_t e = launch_vtable_separate(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? LVKV_OK : hip_fail(e);
+  }
+  if (!d_keys || !d_key_off || !d_key_len || !d_vals || !d_val_off || !d_val_len || !d_scratch ||
+      !d_vtb || !d_out_vals || !d_out_val_off || !d_out_val_len || !d_report)
+    return LVKV_ERR_INVALID;
+  if (nentries >= (uint64_t{1} << 31) ||
+      scratch_bytes < lvkv_vtable_separate_scratch_bytes(nentries))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  a.keys = static_cast<const uint8_t*>(d_keys);
+  a.key_off = d_key_off;
+  a.key_len = d_key_len;
+  a.vals = static_cast<const uint8_t*>(d_vals);
+  a.val_off = d_val_off;
+  a.val_len = d_val_len;
+  a.n = static_cast<uint32_t>(nentries);
+  a.kv_sep_size = kv_sep_size;
+  a.file_number = file_number;
+  a.scratch = static_cast<uint8_t*>(d_scratch);
+  a.vtb = static_cast<uint8_t*>(d_vtb);
+  a.vtb_capacity = vtb_capacity;
+  a.out_vals = static_cast<uint8_t*>(d_out_vals);
+  a.out_val_capacity = out_val_capacity;
+  a.out_val_off = d_out_val_off;
+  a.out_val_len = d_out_val_len;
+  a.rec_off = d_rec_off;
+  a.rec_size = d_rec_size;
+  const hipError_t e = launch_vtable_separate(a, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
+size_t lvkv_vtable_resolve_scratch_bytes(size_t nqueries) {
+  return vtable_resolve_scratch_bytes(nqueries);
+}
+
+int lvkv_vtable_resolve_device(const void* d_vals, const uint64_t* d_val_off,
+                               const uint32_t* d_val_len, const uint8_t* d_state,
+                               size_t nqueries, const void* d_vtb, const uint64_t* d_file_off,
+                               const uint64_t* d_file_size, const uint64_t* d_file_number,
+                               size_t nfiles, void* d_scratch, size_t scratch_bytes,
+                               uint8_t* d_status, uint8_t* d_out_src, uint64_t* d_out_off,
+                               uint32_t* d_out_len, lvkv_vtable_resolve_report* d_report,
+                               void* stream) {
+  VtableResolveArgs a{};
+  a.report = d_report;
+  if (nqueries == 0) {
+    if (!d_report) return LVKV_OK;
+    int rc = LVKV_OK;
+    if (current_ctx(&rc) == nullptr) return rc;
+    const hipError_t e = launch_vtable_resolve(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? LVKV_OK : hip_fail(e);
+  }
+  if (!d_vals || !d_val_off || !d_val_len || !d_scratch || !d_status || !d_out_src ||
+      !d_out_off || !d_out_len || !d_report)
+    return LVKV_ERR_INVALID;
+  if (nfiles != 0 && (!d_vtb || !d_file_off || !d_file_size || !d_file_number))
+    return LVKV_ERR_INVALID;
+  if (nqueries >= (uint64_t{1} << 31) || nfiles >= (uint64_t{1} << 31) ||
+      scratch_bytes < lvkv_vtable_resolve_scratch_bytes(nqueries))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  a.vals = static_cast<const uint8_t*>(d_vals);
+  a.val_off = d_val_off;
+  a.val_len = d_val_len;
+  a.state = d_state;
+  a.n = static_cast<uint32_t>(nqueries);
+  a.vtb = static_cast<const uint8_t*>(d_vtb);
+  a.file_off = d_file_off;
+  a.file_size = d_file_size;
+  a.file_number = d_file_number;
+  a.nfiles = static_cast<uint32_t>(nfiles);
+  a.scratch = static_cast<uint8_t*>(d_scratch);
+  a.status = d_status;
+  a.out_src = d_out_src;
+  a.out_off = d_out_off;
+  a.out_len = d_out_len;
+  const hipError_t e = launch_vtable_resolve(a, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
+size_t lvkv_vtable_gather_scratch_bytes(size_t nqueries) {
+  return vtable_gather_scratch_bytes(nqueries);
+}
+
+int lvkv_vtable_gather_device(const void* d_vals, const void* d_vtb, const uint8_t* d_status,
+                              const uint8_t* d_out_src, const uint64_t* d_out_off,
+                              const uint32_t* d_out_len, size_t nqueries, void* d_scratch,
+                              size_t scratch_bytes, void* d_dst, uint64_t dst_capacity,
+                              uint64_t* d_dst_off, lvkv_vtable_gather_report* d_report,
+                              void* stream) {
+  VtableGatherArgs a{};
+  a.report = d_report;
+  if (nqueries == 0) {
+    if (!d_report) return LVKV_OK;
+    int rc = LVKV_OK;
+    if (current_ctx(&rc) == nullptr) return rc;
+    const hipError_t e = launch_vtable_gather(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? LVKV_OK : hip_fail(e);
+  }
+  if (!d_vals || !d_vtb || !d_status || !d_out_src || !d_out_off || !d_out_len || !d_scratch ||
+      !d_dst || !d_dst_off || !d_report)
+    return LVKV_ERR_INVALID;
+  if (nqueries >= (uint64_t{1} << 31) ||
+      scratch_bytes < lvkv_vtable_gather_scratch_bytes(nqueries))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  a.vals = static_cast<const uint8_t*>(d_vals);
+  a.vtb = static_cast<const uint8_t*>(d_vtb);
+  a.status = d_status;
+  a.out_src = d_out_src;
+  a.out_off = d_out_off;
+  a.out_len = d_out_len;
+  a.n = static_cast<uint32_t>(nqueries);
+  a.scratch = static_cast<uint8_t*>(d_scratch);
+  a.dst = static_cast<uint8_t*>(d_dst);
+  a.dst_capacity = dst_capacity;
+  a.dst_off = d_dst_off;
+  const hipError_t e = launch_vtable_gather(a, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
 int lvkv_sst_write_blocks_device(const void* d_raw, const uint64_t* d_raw_off,
                                  const uint32_t* d_raw_len, size_t nblocks, int compression,
                                  uint32_t max_len, void* d_scratch, void* d_file,
@@ -1642,6 +1796,10 @@ int lvkv_debug_set_general_kernel(int k) {
 }
 
 // The ragged cfg used for WAL records (8, 16, 24: small-record shapes).
+int lvkv_debug_set_vtable_copy_rows(int rows) {
+  return vtable_set_copy_rows(rows) ? LVKV_OK : LVKV_ERR_INVALID;
+}
+
 int lvkv_debug_set_log_kernel(int k) {
   if (k < 0 || k > 31) return LVKV_ERR_INVALID;
   int rc = LVKV_OK;

@@ -15,6 +15,7 @@
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
 #include "lvkv_snappy.h"
+#include "lvkv_vtable.h"
 
 namespace lvkv {
 
@@ -381,6 +382,71 @@ struct SstGetSeekArgs {
   lvkv_sst_get_seek_report* report;
 };
 hipError_t launch_sst_get_seek(const SstGetSeekArgs& a, hipStream_t stream);
+
+// ---- KV separation on the device (lvkv_vtable.hip) -------------------------------
+
+// lvkv_vtable_*_scratch_bytes: the call's arrays and alignment slack.
+size_t vtable_separate_scratch_bytes(size_t nentries);
+size_t vtable_resolve_scratch_bytes(size_t nqueries);
+size_t vtable_gather_scratch_bytes(size_t nqueries);
+struct VtableSeparateArgs {
+  const uint8_t* keys;
+  const uint64_t* key_off;
+  const uint32_t* key_len;
+  const uint8_t* vals;
+  const uint64_t* val_off;
+  const uint32_t* val_len;
+  uint32_t n;
+  uint64_t kv_sep_size, file_number;
+  uint8_t* scratch;  // the caller's, vtable_separate_scratch_bytes long
+  uint8_t* vtb;
+  uint64_t vtb_capacity;
+  uint8_t* out_vals;
+  uint64_t out_val_capacity;
+  uint64_t* out_val_off;
+  uint32_t* out_val_len;
+  uint64_t* rec_off;   // may be null
+  uint64_t* rec_size;  // may be null
+  lvkv_vtable_separate_report* report;
+};
+hipError_t launch_vtable_separate(const VtableSeparateArgs& a, hipStream_t stream);
+struct VtableResolveArgs {
+  const uint8_t* vals;
+  const uint64_t* val_off;
+  const uint32_t* val_len;
+  const uint8_t* state;  // may be null
+  uint32_t n;
+  const uint8_t* vtb;
+  const uint64_t* file_off;
+  const uint64_t* file_size;
+  const uint64_t* file_number;
+  uint32_t nfiles;
+  uint8_t* scratch;  // the caller's, vtable_resolve_scratch_bytes long
+  uint8_t* status;
+  uint8_t* out_src;
+  uint64_t* out_off;
+  uint32_t* out_len;
+  lvkv_vtable_resolve_report* report;
+};
+hipError_t launch_vtable_resolve(const VtableResolveArgs& a, hipStream_t stream);
+struct VtableGatherArgs {
+  const uint8_t* vals;
+  const uint8_t* vtb;
+  const uint8_t* status;
+  const uint8_t* out_src;
+  const uint64_t* out_off;
+  const uint32_t* out_len;
+  uint32_t n;
+  uint8_t* scratch;  // the caller's, vtable_gather_scratch_bytes long
+  uint8_t* dst;
+  uint64_t dst_capacity;
+  uint64_t* dst_off;  // n + 1
+  lvkv_vtable_gather_report* report;
+};
+hipError_t launch_vtable_gather(const VtableGatherArgs& a, hipStream_t stream);
+// The copy kernel's tile for the calls that follow, in 16-byte stores a lane
+// (1, 2, 4, 8; 0: the production choice). Measurement only (tools/vtable_bench.py).
+bool vtable_set_copy_rows(int rows);
 
 #ifdef LVKV_PROBE_BUILD
 // Probe builds (tools/probe/liblvkv_probe.so): timestamp buffers and knobs
