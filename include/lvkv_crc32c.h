@@ -124,11 +124,12 @@ int lvkv_engine_create(int device, lvkv_engine** out);
 void lvkv_engine_destroy(lvkv_engine* engine);
 /* lvkv_crc32c_uniform_device's contract, asynchronous on the engine, for any
  * length, stride and alignment and any nblocks (batches beyond one
- * dispatch's capacity become several dispatches). Blocks of 4..4348 bytes
- * (16 rows of 256 B) whose ends are 4-byte aligned ((d_base + length) % 4 ==
- * 0, stride % 4 == 0) — the headline's 4 KiB blocks — run the burst kernel;
- * other shapes (32 KiB WAL blocks at +6, odd lengths) the general walk of
- * lvkv_engine_crc32c_batch in its uniform layout. */
+ * dispatch's capacity become several dispatches). Blocks of 4..4096 bytes
+ * (at most 16 rows of 256 B on the word grid aligned to the block's end)
+ * whose ends are 4-byte aligned ((d_base + length) % 4 == 0, stride % 4 ==
+ * 0) — the headline's 4 KiB blocks — run the burst kernel; other shapes
+ * (over 4096 bytes, 32 KiB WAL blocks at +6, unaligned ends) the general walk
+ * of lvkv_engine_crc32c_batch in its uniform layout. */
 int lvkv_engine_crc32c_uniform(lvkv_engine* engine, const void* d_base, uint64_t stride,
                                uint32_t length, uint32_t init, uint32_t* d_out,
                                size_t nblocks, uint32_t flags);

@@ -11,8 +11,10 @@
 //
 // Work map: the batch is split into gridDim.x contiguous runs of equal length
 // (+1 for the first nblocks % G); run element i goes to wave i % W, chain
-// i / W, so a wave's valid chains are a prefix. Blocks are <= 16 rows
-// (4 KiB + 252 B); the host checks n <= G * W * NCH.
+// i / W, so a wave's valid chains are a prefix. Blocks are 4..4096 bytes with
+// 4-byte aligned ends: <= 16 rows of the end-aligned grid, the first row
+// short by s0l words and the first word by delta bytes. The host routes every
+// other shape to the general walk and checks n <= G * W * NCH.
 //
 // vmcnt discipline: the lane-column load is issued first, then the rows in
 // walk order, all unconditionally (rows past a short block are outside its
