@@ -230,6 +230,13 @@ def _load() -> ctypes.CDLL:
     L.lvkv_vtable_gather_scratch_bytes.restype = sz
     L.lvkv_vtable_gather_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, u64, vp, vp, vp]
     L.lvkv_vtable_gather_device.restype = i32
+    L.lvkv_memtable_scratch_bytes.argtypes = [sz, sz]
+    L.lvkv_memtable_scratch_bytes.restype = sz
+    L.lvkv_memtable_from_batches_device.argtypes = [vp, vp, vp, sz, u64, u32, vp, sz, vp, u64, vp,
+                                                    vp, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.lvkv_memtable_from_batches_device.restype = i32
+    L.lvkv_debug_set_memtable_tile.argtypes = [i32]
+    L.lvkv_debug_set_memtable_tile.restype = i32
     L.lvkv_strerror.argtypes = [i32]
     L.lvkv_strerror.restype = ctypes.c_char_p
     L.lvkv_last_hip_error.argtypes = []
@@ -1776,6 +1783,128 @@ def sst_get_values(file, vtables, qkeys, qkey_off, qkey_len, *, stream=None, **g
     res.update(values=values, value_off=value_off, status=status, state=got["state"],
                resolve=rrep, gather=grep)
     return res
+
+
+(MEMTABLE_OK, MEMTABLE_TOO_SMALL, MEMTABLE_UNKNOWN_TAG, MEMTABLE_BAD_PUT, MEMTABLE_BAD_DELETE,
+ MEMTABLE_WRONG_COUNT, MEMTABLE_KEY_TOO_LONG, MEMTABLE_CAPACITY, MEMTABLE_DUPLICATE) = range(9)
+MEMTABLE_NONE = 0xFFFFFFFF
+MEMTABLE_PARANOID = 1
+# where the device call changes path with the sizes (csrc/lvkv_launch.h)
+MEMTABLE_WINDOW = 8192    # bytes of a batch its wave holds in LDS at a time
+MEMTABLE_SORT_TILE = 1024  # pairs a workgroup sorts in LDS
+
+
+class MemtableReport(ctypes.Structure):
+    """lvkv_memtable_report (include/lvkv_memtable.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("first_bad_batch", ctypes.c_uint32),
+                ("first_bad_entry", ctypes.c_uint32), ("nentries", ctypes.c_uint32),
+                ("key_bytes", ctypes.c_uint64), ("val_bytes", ctypes.c_uint64),
+                ("max_key_len", ctypes.c_uint32), ("n_too_small", ctypes.c_uint32),
+                ("too_small_bytes", ctypes.c_uint64), ("max_sequence_out", ctypes.c_uint64),
+                ("n_bad_batches", ctypes.c_uint32), ("reserved_", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
+def memtable_from_batches(payload, batch_off, batch_len, *, max_sequence: int = 0,
+                          paranoid: bool = False, max_entries: Optional[int] = None,
+                          key_capacity: Optional[int] = None, scratch=None, stream=None):
+    """RecoverLogFile's loop over the write batches of a WAL
+    (lvkv_memtable_from_batches_device): batch b is payload[batch_off[b] :
+    + batch_len[b]] (int64 tensors; log_read(gather=True)'s payload, its
+    positions and its records' lengths). Every batch is walked as
+    WriteBatch::Iterate walks it, every entry met gets MemTable::Add's internal
+    key, and the entries come out in the memtable's iteration order.
+
+    Returns (report dict, keys, key_off int64, key_len int32, vals, val_off
+    int64, val_len int32, src int32, batch_status uint8, batch_entries int32):
+    the six entry arrays are sst_build_blocks' and vtable_separate's arguments
+    (vals is `payload`: no value byte is copied; keys holds the internal keys
+    in log order), src[i] the log-order index of sorted entry i. The per-entry
+    arrays are cut to the report's nentries, and are empty unless its status is
+    MEMTABLE_OK. The default capacities always fit: entries <= payload bytes /
+    2, key bytes <= payload bytes + 8 * entries. The report is the one thing
+    read back."""
+    torch = _torch()
+    nb = batch_off.numel()
+    dev = payload.device
+    if batch_len.numel() != nb:
+        raise ValueError("batch_off and batch_len differ in length")
+    if max_entries is None or key_capacity is None:
+        pb = min(int(batch_len.sum().item()), payload.numel()) if nb else 0
+        if max_entries is None:
+            max_entries = pb // 2
+        if key_capacity is None:
+            key_capacity = pb + 8 * max_entries
+    if scratch is None:
+        scratch = torch.empty(int(_lib.lvkv_memtable_scratch_bytes(nb, max_entries)),
+                              dtype=torch.uint8, device=dev)
+    slots = max(1, max_entries)
+    keys = torch.empty(max(1, key_capacity), dtype=torch.uint8, device=dev)
+    key_off = torch.empty(slots, dtype=torch.int64, device=dev)
+    key_len = torch.empty(slots, dtype=torch.int32, device=dev)
+    val_off = torch.empty(slots, dtype=torch.int64, device=dev)
+    val_len = torch.empty(slots, dtype=torch.int32, device=dev)
+    src = torch.empty(slots, dtype=torch.int32, device=dev)
+    bst = torch.empty(max(1, nb), dtype=torch.uint8, device=dev)
+    bent = torch.empty(max(1, nb), dtype=torch.int32, device=dev)
+    rep = torch.zeros(ctypes.sizeof(MemtableReport), dtype=torch.uint8, device=dev)
+    b8 = (torch.uint8, torch.int8)
+    i64 = (torch.int64,)
+    with torch.cuda.device(dev):
+        rc = _lib.lvkv_memtable_from_batches_device(
+            _dev_ptr(payload, "payload", b8) if nb else None,
+            _dev_ptr(batch_off, "batch_off", i64) if nb else None,
+            _dev_ptr(batch_len, "batch_len", i64) if nb else None, nb,
+            int(max_sequence), MEMTABLE_PARANOID if paranoid else 0,
+            _dev_ptr(scratch, "scratch", b8), scratch.numel(), _dev_ptr(keys, "keys"),
+            int(key_capacity), _dev_ptr(key_off, "key_off"), _dev_ptr(key_len, "key_len"),
+            _dev_ptr(val_off, "val_off"), _dev_ptr(val_len, "val_len"), _dev_ptr(src, "src"),
+            int(max_entries), _dev_ptr(bst, "batch_status"), _dev_ptr(bent, "batch_entries"),
+            _dev_ptr(rep, "report"), _stream_handle(stream, dev))
+    _check("lvkv_memtable_from_batches_device", rc)
+    report = _read_report(MemtableReport, rep, stream)
+    n = report["nentries"] if report["status"] == MEMTABLE_OK else 0
+    return (report, keys, key_off[:n], key_len[:n], payload, val_off[:n], val_len[:n], src[:n],
+            bst[:nb], bent[:nb])
+
+
+def wal_recover_table(log_image, *, file_number: int, kv_sep_size: int, paranoid: bool = False,
+                      max_sequence: int = 0, stream=None, **build_options):
+    """A WAL image in device memory -> the level-0 table and vTable images
+    DBImpl::RecoverLogFile writes for it (one memtable: the reference's switch
+    to a new one at write_buffer_size is the caller's), no entry crossing to
+    the host: log_read(gather=True), memtable_from_batches on its records,
+    sst_flush_separated on the sorted entries (build_options: its
+    table_options). Returns (table image, vTable image, reports, max_sequence);
+    reports = {'log', 'log_corruptions', 'memtable', 'separate', 'build',
+    'table'}. Both images are None when nothing is written: no entry was
+    inserted (BuildTable removes the file), or -- paranoid -- a batch was bad
+    or the log reader reported a corruption (max_sequence is then None: the
+    reference stops at the report, and which batches came before it is not
+    looked at here). The vTable image is empty when no value moved. The
+    reports of the calls are read on the host in between."""
+    torch = _torch()
+    dev = log_image.device
+    rd, records, corruptions, _, (payload, pos) = log_read(log_image, gather=True, stream=stream)
+    reports = {"log": rd, "log_corruptions": corruptions, "memtable": None, "separate": None,
+               "build": None, "table": None}
+    if rd["status"] != 0:
+        raise ValueError(f"the log does not read: {rd}")
+    if paranoid and corruptions:
+        return None, None, reports, None
+    lens = torch.tensor([r[1] for r in records], dtype=torch.int64, device=dev)
+    m = memtable_from_batches(payload, pos, lens, max_sequence=max_sequence, paranoid=paranoid,
+                              stream=stream)
+    reports["memtable"] = m[0]
+    if m[0]["status"] != MEMTABLE_OK or m[0]["nentries"] == 0:
+        return None, None, reports, m[0]["max_sequence_out"]
+    table, vtb, flush = sst_flush_separated(*m[1:7], kv_sep_size=kv_sep_size,
+                                            file_number=file_number, stream=stream,
+                                            **build_options)
+    reports.update(flush)
+    return table, vtb, reports, m[0]["max_sequence_out"]
 
 
 def sst_compact_tables(files, *, smallest_snapshot: int, deeper=None,

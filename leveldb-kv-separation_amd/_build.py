@@ -42,7 +42,7 @@ HIP_SOURCES = ["crc32c_kernel.hip", "crc32c_uniform.hip", "crc32c_compact.hip",
                "lvkv_log_assemble.hip", "lvkv_snappy.hip", "lvkv_sst_blocks.hip", "lvkv_zstd.hip",
                "lvkv_zstd_compress.hip", "lvkv_sst_finish.hip", "lvkv_sst_build.hip",
                "lvkv_sst_entries.hip", "lvkv_sst_merge.hip", "lvkv_sst_get.hip", "lvkv_vtable.hip",
-               "lvkv_capi.cpp",
+               "lvkv_memtable.hip", "lvkv_capi.cpp",
                "lvkv_engine.cpp"]
 # Kernels of the AQL engine: compiled alone into a gfx950 code object that is
 # embedded in the library (.incbin) and loaded through the HSA loader.
@@ -50,7 +50,8 @@ ENGINE_KERNELS = "lvkv_engine_kernels.hip"
 HEADERS = ["lvkv_kernel_args.h", "lvkv_tables.h", "crc32c_device_common.h",
            "crc32c_uniform_common.h", "crc32c_compact_common.h", "crc32c_burst.h",
            "crc32c_ragged_body.h", "crc32c_modes.h", "lvkv_log_events.h", "lvkv_zstd_tables.h", "lvkv_launch.h",
-           "lvkv_block_scan.h", "lvkv_scratch.h", "lvkv_table_format.h", "lvkv_lds_bytes.h"]
+           "lvkv_block_scan.h", "lvkv_scratch.h", "lvkv_table_format.h", "lvkv_lds_bytes.h",
+           "lvkv_image_copy.h", "lvkv_key_compare.h"]
 
 
 def _run(cmd: list[str], verbose: bool) -> None:

@@ -1475,6 +1475,61 @@ int lvkv_vtable_gather_device(const void* d_vals, const void* d_vtb, const uint8
   return e == hipSuccess ? LVKV_OK : hip_fail(e);
 }
 
+size_t lvkv_memtable_scratch_bytes(size_t nbatches, size_t max_entries) {
+  return memtable_scratch_bytes(nbatches, max_entries);
+}
+
+int lvkv_debug_set_memtable_tile(int pairs) {
+  return memtable_set_tile(pairs) ? LVKV_OK : LVKV_ERR_INVALID;
+}
+
+int lvkv_memtable_from_batches_device(const void* d_payload, const uint64_t* d_batch_off,
+                                      const uint64_t* d_batch_len, size_t nbatches,
+                                      uint64_t max_sequence_in, uint32_t flags, void* d_scratch,
+                                      size_t scratch_bytes, void* d_keys, uint64_t key_capacity,
+                                      uint64_t* d_key_off, uint32_t* d_key_len,
+                                      uint64_t* d_val_off, uint32_t* d_val_len, uint32_t* d_src,
+                                      size_t max_entries, uint8_t* d_batch_status,
+                                      uint32_t* d_batch_entries, lvkv_memtable_report* d_report,
+                                      void* stream) {
+  MemtableArgs a{};
+  a.report = d_report;
+  a.max_sequence_in = max_sequence_in;
+  if (nbatches == 0) {
+    if (!d_report) return LVKV_OK;
+    int rc = LVKV_OK;
+    if (current_ctx(&rc) == nullptr) return rc;
+    const hipError_t e = launch_memtable(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? LVKV_OK : hip_fail(e);
+  }
+  if (!d_payload || !d_batch_off || !d_batch_len || !d_scratch || !d_keys || !d_key_off ||
+      !d_key_len || !d_val_off || !d_val_len || !d_src || !d_report)
+    return LVKV_ERR_INVALID;
+  if (nbatches >= (uint64_t{1} << 31) || max_entries >= (uint64_t{1} << 31) ||
+      scratch_bytes < lvkv_memtable_scratch_bytes(nbatches, max_entries))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  a.payload = static_cast<const uint8_t*>(d_payload);
+  a.batch_off = d_batch_off;
+  a.batch_len = d_batch_len;
+  a.nbatches = static_cast<uint32_t>(nbatches);
+  a.flags = flags;
+  a.scratch = static_cast<uint8_t*>(d_scratch);
+  a.keys = static_cast<uint8_t*>(d_keys);
+  a.key_capacity = key_capacity;
+  a.key_off = d_key_off;
+  a.key_len = d_key_len;
+  a.val_off = d_val_off;
+  a.val_len = d_val_len;
+  a.src = d_src;
+  a.max_entries = static_cast<uint32_t>(max_entries);
+  a.batch_status = d_batch_status;
+  a.batch_entries = d_batch_entries;
+  const hipError_t e = launch_memtable(a, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
 int lvkv_sst_write_blocks_device(const void* d_raw, const uint64_t* d_raw_off,
                                  const uint32_t* d_raw_len, size_t nblocks, int compression,
                                  uint32_t max_len, void* d_scratch, void* d_file,

@@ -14,6 +14,7 @@
 
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
+#include "lvkv_memtable.h"
 #include "lvkv_snappy.h"
 #include "lvkv_vtable.h"
 
@@ -447,6 +448,38 @@ hipError_t launch_vtable_gather(const VtableGatherArgs& a, hipStream_t stream);
 // The copy kernel's tile for the calls that follow, in 16-byte stores a lane
 // (1, 2, 4, 8; 0: the production choice). Measurement only (tools/vtable_bench.py).
 bool vtable_set_copy_rows(int rows);
+
+// ---- the memtable on the device (lvkv_memtable.hip) -----------------------------
+
+// Bytes of a batch its wave holds in LDS at a time, and the pairs a workgroup
+// sorts in LDS; the call changes path with the sizes only there.
+constexpr uint32_t kMemtableWindow = 8192;
+constexpr uint32_t kMemtableTile = 1024;
+// lvkv_memtable_scratch_bytes: the call's arrays and alignment slack.
+size_t memtable_scratch_bytes(size_t nbatches, size_t max_entries);
+struct MemtableArgs {
+  const uint8_t* payload;
+  const uint64_t* batch_off;
+  const uint64_t* batch_len;
+  uint32_t nbatches, flags;
+  uint64_t max_sequence_in;
+  uint8_t* scratch;  // the caller's, memtable_scratch_bytes long
+  uint8_t* keys;
+  uint64_t key_capacity;
+  uint64_t* key_off;
+  uint32_t* key_len;
+  uint64_t* val_off;
+  uint32_t* val_len;
+  uint32_t* src;
+  uint32_t max_entries;
+  uint8_t* batch_status;    // may be null
+  uint32_t* batch_entries;  // may be null
+  lvkv_memtable_report* report;
+};
+hipError_t launch_memtable(const MemtableArgs& a, hipStream_t stream);
+// The sort tile for the calls that follow (512, 1024, 2048; 0: the production
+// choice). Measurement only (tools/memtable_bench.py).
+bool memtable_set_tile(int pairs);
 
 #ifdef LVKV_PROBE_BUILD
 // Probe builds (tools/probe/liblvkv_probe.so): timestamp buffers and knobs
