@@ -237,6 +237,12 @@ def _load() -> ctypes.CDLL:
     L.lvkv_memtable_from_batches_device.restype = i32
     L.lvkv_debug_set_memtable_tile.argtypes = [i32]
     L.lvkv_debug_set_memtable_tile.restype = i32
+    L.lvkv_sst_scan_entries_scratch_bytes.argtypes = [sz, sz]
+    L.lvkv_sst_scan_entries_scratch_bytes.restype = sz
+    L.lvkv_sst_scan_entries_device.argtypes = [vp, vp, vp, vp, vp, sz, u64, vp, vp, vp, vp, vp, vp,
+                                               sz, vp, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp,
+                                               vp]
+    L.lvkv_sst_scan_entries_device.restype = i32
     L.lvkv_strerror.argtypes = [i32]
     L.lvkv_strerror.restype = ctypes.c_char_p
     L.lvkv_last_hip_error.argtypes = []
@@ -1974,6 +1980,233 @@ def sst_compact_tables(files, *, smallest_snapshot: int, deeper=None,
                             filter_bits_per_key=filter_bits_per_key, file=file,
                             file_capacity=file_capacity, stream=stream)
     return built + (m[6],)
+
+
+SCAN_OK, SCAN_UNSORTED, SCAN_BAD_KEY, SCAN_CAPACITY = range(4)
+SCAN_Q_OK, SCAN_Q_CORRUPT = range(2)
+SCAN_NONE = 0xFFFFFFFF
+SCAN_NO_LIMIT = 0xFFFFFFFF
+MAX_SEQUENCE_NUMBER = (1 << 56) - 1  # kMaxSequenceNumber (db/dbformat.h:69)
+
+
+class SstScanReport(ctypes.Structure):
+    """lvkv_sst_scan_report (include/lvkv_scan.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("first_bad_entry", ctypes.c_uint32),
+                ("num_in", ctypes.c_uint32), ("num_visible", ctypes.c_uint32),
+                ("num_above_snapshot", ctypes.c_uint32), ("num_unparsable", ctypes.c_uint32),
+                ("num_deletions", ctypes.c_uint32), ("num_hidden", ctypes.c_uint32),
+                ("key_bytes", ctypes.c_uint64), ("value_bytes", ctypes.c_uint64),
+                ("nqueries", ctypes.c_uint32), ("max_count", ctypes.c_uint32),
+                ("sum_count", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _pack_user_keys(torch, dev, keys):
+    """[bytes] -> (buffer uint8, offsets, lengths as lists) end to end."""
+    offs, at = [], 0
+    for k in keys:
+        offs.append(at)
+        at += len(k)
+    buf = torch.tensor(list(b"".join(bytes(k) for k in keys)) or [0], dtype=torch.uint8, device=dev)
+    return buf, offs, [len(k) for k in keys]
+
+
+def sst_scan_entries(keys, key_off, key_len, val_off, val_len, *, snapshot: int, qkeys=None,
+                     start_off=None, start_len=None, limit_off=None, limit_len=None, q_max=None,
+                     max_out: Optional[int] = None, stream=None):
+    """DBIter over entries in MergingIterator's order at `snapshot`
+    (lvkv_sst_scan_entries_device): which of them a reader sees, and for a
+    batch of ranges where Seek lands and how many entries the loop `for
+    (it->Seek(start); it->Valid() && n < max && it->key() < limit; it->Next())`
+    counts. The entry arrays are sst_merge_entries' outputs without compact (or
+    one sorted run); keys internal keys. Query q: start qkeys[start_off[q] : +
+    start_len[q]], limit qkeys[limit_off[q] : + limit_len[q]] (user keys;
+    limit_len -1, SCAN_NO_LIMIT as int32: none), q_max[q] (int32 tensor or
+    None: unbounded). Returns a dict: key_off int64 / key_len int32 -- the
+    visible entries' USER keys in `keys` --, val_off / val_len -- their values
+    as stored --, src int32, cut to report['num_visible']; q_first / q_count
+    int32 and q_status uint8 (SCAN_Q_*) per query: its entries are first ..
+    first + count of that list; report. report['status'] is SCAN_*, and the
+    arrays are empty unless it is SCAN_OK. The report is the one thing read
+    back."""
+    torch = _torch()
+    n = key_off.numel()
+    dev = keys.device
+    if not (key_len.numel() == val_off.numel() == val_len.numel() == n):
+        raise ValueError("the entry arrays differ in length")
+    nq = start_off.numel() if start_off is not None else 0
+    if nq and not (start_len.numel() == limit_off.numel() == limit_len.numel() == nq and
+                   (q_max is None or q_max.numel() == nq)):
+        raise ValueError("the query arrays differ in length")
+    if max_out is None:
+        max_out = n
+    scratch = torch.empty(int(_lib.lvkv_sst_scan_entries_scratch_bytes(n, nq)), dtype=torch.uint8,
+                          device=dev)
+    slots = max(1, max_out)
+    out_key_off = torch.empty(slots, dtype=torch.int64, device=dev)
+    out_key_len = torch.empty(slots, dtype=torch.int32, device=dev)
+    out_val_off = torch.empty(slots, dtype=torch.int64, device=dev)
+    out_val_len = torch.empty(slots, dtype=torch.int32, device=dev)
+    src = torch.empty(slots, dtype=torch.int32, device=dev)
+    # (with no entry the call writes no per-query word: every count is 0)
+    q_first = torch.zeros(max(1, nq), dtype=torch.int32, device=dev)
+    q_count = torch.zeros(max(1, nq), dtype=torch.int32, device=dev)
+    q_status = torch.zeros(max(1, nq), dtype=torch.uint8, device=dev)
+    rep = torch.zeros(ctypes.sizeof(SstScanReport), dtype=torch.uint8, device=dev)
+    b8 = (torch.uint8, torch.int8)
+    i64, i32 = (torch.int64,), (torch.int32,)
+    with torch.cuda.device(dev):
+        rc = _lib.lvkv_sst_scan_entries_device(
+            _dev_ptr(keys, "keys", b8) if n else None,
+            _dev_ptr(key_off, "key_off", i64) if n else None,
+            _dev_ptr(key_len, "key_len", i32) if n else None,
+            _dev_ptr(val_off, "val_off", i64) if n else None,
+            _dev_ptr(val_len, "val_len", i32) if n else None, n, int(snapshot),
+            _dev_ptr(qkeys, "qkeys", b8) if nq else None,
+            _dev_ptr(start_off, "start_off", i64) if nq else None,
+            _dev_ptr(start_len, "start_len", i32) if nq else None,
+            _dev_ptr(limit_off, "limit_off", i64) if nq else None,
+            _dev_ptr(limit_len, "limit_len", i32) if nq else None,
+            _dev_ptr(q_max, "q_max", i32) if nq and q_max is not None else None, nq,
+            _dev_ptr(scratch, "scratch", b8), scratch.numel(),
+            _dev_ptr(out_key_off, "out_key_off"), _dev_ptr(out_key_len, "out_key_len"),
+            _dev_ptr(out_val_off, "out_val_off"), _dev_ptr(out_val_len, "out_val_len"),
+            _dev_ptr(src, "src"), int(max_out), _dev_ptr(q_first, "q_first"),
+            _dev_ptr(q_count, "q_count"), _dev_ptr(q_status, "q_status"), _dev_ptr(rep, "report"),
+            _stream_handle(stream, dev))
+    _check("lvkv_sst_scan_entries_device", rc)
+    report = _read_report(SstScanReport, rep, stream)
+    ok = report["status"] == SCAN_OK
+    nv = report["num_visible"] if ok else 0
+    nq = nq if ok else 0
+    return dict(key_off=out_key_off[:nv], key_len=out_key_len[:nv], val_off=out_val_off[:nv],
+                val_len=out_val_len[:nv], src=src[:nv], q_first=q_first[:nq], q_count=q_count[:nq],
+                q_status=q_status[:nq], report=report)
+
+
+def _read_run(img, i, *, filter_policy, max_ulen, verify, stream):
+    """The entries of table image i as sst_read_table lists them, with the
+    table nothing was added to taken for what it is (sst_compact_tables says
+    why). An image or a block that does not read raises ValueError."""
+    table, off, size, _, _ = sst_verify_table(img, filter_policy=filter_policy, stream=stream)
+    if table["status"] != 0:
+        raise ValueError(f"input table {i} does not open: status {table['status']}")
+    nd = 0 if table["ndata"] == 1 and table["index_size"] == 8 else table["ndata"]
+    out, out_off, out_len, rstatus = sst_read_blocks(img, off[:nd], size[:nd], max_ulen=max_ulen,
+                                                     verify=verify, stream=stream)
+    t = sst_read_entries(out, out_off, out_len, skip=rstatus, stream=stream)
+    if t[8]["status"] != 0 or t[8]["nbad"] != 0 or bool(rstatus.any().item()):
+        raise ValueError(f"input table {i} has a block that does not read: block status "
+                         f"{rstatus.tolist()}, entries report {t[8]}")
+    return t[:6]
+
+
+def db_scan(files, vtables, starts, limits, *, snapshot: int, memtable=None, max_count=None,
+            reverse: bool = False, filter_policy: Optional[str] = None, max_ulen: int,
+            verify: bool = True, stream=None):
+    """DB::NewIterator at `snapshot` and, per range, the loop `for
+    (it->Seek(start); it->Valid() && n < max && it->key() < limit; it->Next())`
+    with DBIter::fields()' DecodeValue on each value, over table images in
+    device memory and no entry crossing to the host: sst_read_table's steps on
+    each image (a run an image, in the order given: newer files first, as
+    Version::AddIterators lists level 0), before them as run 0 the `memtable`
+    entries (memtable_from_batches' six entry arrays), sst_merge_entries
+    without compact, sst_scan_entries, then vtable_resolve and vtable_gather on
+    the selected entries' values against `vtables` ({file number: vTable
+    image}) and vtable_gather again on the key buffer for the user keys.
+    starts / limits: user keys as bytes, a limit of None for no limit;
+    max_count: None, one int, or one int or None a range. A Get of key k across
+    the runs is the range (k, k + b'\\0', 1).
+
+    Returns a dict: query_off (int64 of nq + 1: range q's entries are
+    query_off[q] .. query_off[q + 1] of the lists), keys / key_off (int64 of
+    total + 1: entry e's user key is keys[key_off[e] : key_off[e + 1]]), values
+    / value_off likewise (the value DecodeValue leaves: empty unless status[e]
+    is VRES_OK), status (uint8 VRES_* an entry), q_status (uint8 SCAN_Q_* a
+    range), and the reports merge, scan, resolve, gather. With reverse=True a
+    range's entries come last first (the slice the SeekToLast / Prev walk
+    crosses: over sorted entries that walk yields the forward list backwards).
+    When the merge or the scan does not end OK only the reports are there.
+    The per-range index lists are built on the device; the reports are read on
+    the host in between."""
+    torch = _torch()
+    if len(starts) != len(limits):
+        raise ValueError("starts and limits differ in length")
+    nq = len(starts)
+    if max_count is None or isinstance(max_count, int):
+        max_count = [max_count] * nq
+    if len(max_count) != nq:
+        raise ValueError("max_count and starts differ in length")
+    parts, run_first = [], [0]
+    key_base = val_base = 0
+    runs = ([tuple(memtable[:6])] if memtable is not None else []) + \
+        [_read_run(img, i, filter_policy=filter_policy, max_ulen=max_ulen, verify=verify,
+                   stream=stream) for i, img in enumerate(files)]
+    if not runs:
+        raise ValueError("no input runs")
+    for keys, key_off, key_len, vals, val_off, val_len in runs:
+        kb = (keys.numel() + 7) & ~7  # the next run's keys stay 8 bytes apart
+        parts.append((torch.cat([keys, keys.new_zeros(kb - keys.numel())]), key_off + key_base,
+                      key_len, vals, val_off + val_base, val_len))
+        key_base += kb
+        val_base += vals.numel()
+        run_first.append(run_first[-1] + key_off.numel())
+    keys, key_off, key_len, vals, val_off, val_len = (torch.cat([p[k] for p in parts])
+                                                      for k in range(6))
+    dev = keys.device
+    m = sst_merge_entries(keys, key_off, key_len, vals, val_off, val_len,
+                          torch.tensor(run_first, dtype=torch.int64, device=dev), key_format=1,
+                          stream=stream)
+    res = {"merge": m[6]}
+    if m[6]["status"] != MERGE_OK:
+        return res
+    qbuf, offs, lens = _pack_user_keys(torch, dev, list(starts) + [l or b"" for l in limits])
+    i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+    s = sst_scan_entries(
+        keys, m[0], m[1], m[2], m[3], snapshot=snapshot, qkeys=qbuf,
+        start_off=i64(offs[:nq]), start_len=i32(lens[:nq]), limit_off=i64(offs[nq:]),
+        limit_len=i32([-1 if l is None else len(l) for l in limits]),
+        q_max=i32([-1 if c is None else min(int(c), 0x7FFFFFFF) for c in max_count]),
+        stream=stream) if nq else None
+    if nq == 0:
+        res["scan"] = None
+        total = 0
+    else:
+        res["scan"] = s["report"]
+        if s["report"]["status"] != SCAN_OK:
+            return res
+        total = s["report"]["sum_count"]
+    query_off = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    empty8 = torch.zeros(0, dtype=torch.uint8, device=dev)
+    res.update(query_off=query_off, keys=empty8, key_off=query_off[:1].clone(), values=empty8,
+               value_off=query_off[:1].clone(), status=empty8,
+               q_status=s["q_status"] if nq else empty8, resolve=None, gather=None)
+    if total == 0:
+        return res
+    # the entries of range q: slots first[q] .. first[q] + count[q] of the
+    # visible list, end to end (last first with reverse)
+    count = s["q_count"].to(torch.int64)
+    query_off[1:] = torch.cumsum(count, 0)
+    q_of = torch.repeat_interleave(torch.arange(nq, device=dev), count, output_size=total)
+    within = torch.arange(total, device=dev) - query_off[q_of]
+    if reverse:
+        within = count[q_of] - 1 - within
+    sel = s["q_first"].to(torch.int64)[q_of] + within
+    vtb, foff, fsize, fnum = _pack_vtables(torch, dev, vtables)
+    status, src, off, ln, rrep = vtable_resolve(vals, s["val_off"][sel].contiguous(),
+                                                s["val_len"][sel].contiguous(), vtb, foff, fsize,
+                                                fnum, stream=stream)
+    values, value_off, grep = vtable_gather(vals, vtb, status, src, off, ln, stream=stream)
+    # the user keys: a gather from the key buffer, every entry in it
+    zeros = torch.zeros(total, dtype=torch.uint8, device=dev)
+    ukeys, ukey_off, _ = vtable_gather(keys, keys, zeros, zeros, s["key_off"][sel].contiguous(),
+                                       s["key_len"][sel].contiguous(), stream=stream)
+    res.update(keys=ukeys, key_off=ukey_off, values=values, value_off=value_off, status=status,
+               resolve=rrep, gather=grep)
+    return res
 
 
 class LogReport(ctypes.Structure):

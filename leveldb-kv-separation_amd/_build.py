@@ -42,7 +42,7 @@ HIP_SOURCES = ["crc32c_kernel.hip", "crc32c_uniform.hip", "crc32c_compact.hip",
                "lvkv_log_assemble.hip", "lvkv_snappy.hip", "lvkv_sst_blocks.hip", "lvkv_zstd.hip",
                "lvkv_zstd_compress.hip", "lvkv_sst_finish.hip", "lvkv_sst_build.hip",
                "lvkv_sst_entries.hip", "lvkv_sst_merge.hip", "lvkv_sst_get.hip", "lvkv_vtable.hip",
-               "lvkv_memtable.hip", "lvkv_capi.cpp",
+               "lvkv_memtable.hip", "lvkv_sst_scan.hip", "lvkv_capi.cpp",
                "lvkv_engine.cpp"]
 # Kernels of the AQL engine: compiled alone into a gfx950 code object that is
 # embedded in the library (.incbin) and loaded through the HSA loader.

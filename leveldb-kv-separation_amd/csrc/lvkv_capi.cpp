@@ -1530,6 +1530,72 @@ int lvkv_memtable_from_batches_device(const void* d_payload, const uint64_t* d_b
   return e == hipSuccess ? LVKV_OK : hip_fail(e);
 }
 
+size_t lvkv_sst_scan_entries_scratch_bytes(size_t nentries, size_t nqueries) {
+  return sst_scan_scratch_bytes(nentries, nqueries);
+}
+
+int lvkv_sst_scan_entries_device(const void* d_keys, const uint64_t* d_key_off,
+                                 const uint32_t* d_key_len, const uint64_t* d_val_off,
+                                 const uint32_t* d_val_len, size_t nentries, uint64_t snapshot,
+                                 const void* d_qkeys, const uint64_t* d_start_off,
+                                 const uint32_t* d_start_len, const uint64_t* d_limit_off,
+                                 const uint32_t* d_limit_len, const uint32_t* d_q_max,
+                                 size_t nqueries, void* d_scratch, size_t scratch_bytes,
+                                 uint64_t* d_out_key_off, uint32_t* d_out_key_len,
+                                 uint64_t* d_out_val_off, uint32_t* d_out_val_len,
+                                 uint32_t* d_out_src, size_t max_out, uint32_t* d_q_first,
+                                 uint32_t* d_q_count, uint8_t* d_q_status,
+                                 lvkv_sst_scan_report* d_report, void* stream) {
+  SstScanArgs a{};
+  a.report = d_report;
+  if (nentries == 0) {
+    if (!d_report) return LVKV_OK;
+    int rc = LVKV_OK;
+    if (current_ctx(&rc) == nullptr) return rc;
+    const hipError_t e = launch_sst_scan(a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? LVKV_OK : hip_fail(e);
+  }
+  if (!d_keys || !d_key_off || !d_key_len || !d_val_off || !d_val_len || !d_scratch ||
+      !d_out_key_off || !d_out_key_len || !d_out_val_off || !d_out_val_len || !d_out_src ||
+      !d_report)
+    return LVKV_ERR_INVALID;
+  if (nqueries != 0 && (!d_qkeys || !d_start_off || !d_start_len || !d_limit_off ||
+                        !d_limit_len || !d_q_first || !d_q_count || !d_q_status))
+    return LVKV_ERR_INVALID;
+  if (snapshot > (uint64_t{1} << 56) - 1 || nentries >= (uint64_t{1} << 31) ||
+      nqueries >= (uint64_t{1} << 31) ||
+      scratch_bytes < lvkv_sst_scan_entries_scratch_bytes(nentries, nqueries))
+    return LVKV_ERR_INVALID;
+  int rc = LVKV_OK;
+  if (current_ctx(&rc) == nullptr) return rc;
+  a.keys = static_cast<const uint8_t*>(d_keys);
+  a.key_off = d_key_off;
+  a.key_len = d_key_len;
+  a.val_off = d_val_off;
+  a.val_len = d_val_len;
+  a.n = static_cast<uint32_t>(nentries);
+  a.snapshot = snapshot;
+  a.qkeys = static_cast<const uint8_t*>(d_qkeys);
+  a.start_off = d_start_off;
+  a.start_len = d_start_len;
+  a.limit_off = d_limit_off;
+  a.limit_len = d_limit_len;
+  a.q_max = d_q_max;
+  a.nq = static_cast<uint32_t>(nqueries);
+  a.scratch = static_cast<uint8_t*>(d_scratch);
+  a.out_key_off = d_out_key_off;
+  a.out_key_len = d_out_key_len;
+  a.out_val_off = d_out_val_off;
+  a.out_val_len = d_out_val_len;
+  a.out_src = d_out_src;
+  a.max_out = max_out;
+  a.q_first = d_q_first;
+  a.q_count = d_q_count;
+  a.q_status = d_q_status;
+  const hipError_t e = launch_sst_scan(a, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? LVKV_OK : hip_fail(e);
+}
+
 int lvkv_sst_write_blocks_device(const void* d_raw, const uint64_t* d_raw_off,
                                  const uint32_t* d_raw_len, size_t nblocks, int compression,
                                  uint32_t max_len, void* d_scratch, void* d_file,

@@ -15,6 +15,7 @@
 #include "lvkv_crc32c.h"
 #include "lvkv_kernel_args.h"
 #include "lvkv_memtable.h"
+#include "lvkv_scan.h"
 #include "lvkv_snappy.h"
 #include "lvkv_vtable.h"
 
@@ -480,6 +481,39 @@ hipError_t launch_memtable(const MemtableArgs& a, hipStream_t stream);
 // The sort tile for the calls that follow (512, 1024, 2048; 0: the production
 // choice). Measurement only (tools/memtable_bench.py).
 bool memtable_set_tile(int pairs);
+
+// ---- DBIter over merged entries at a snapshot (lvkv_sst_scan.hip) ----------------
+
+// lvkv_sst_scan_entries_scratch_bytes: the call's arrays and alignment slack.
+size_t sst_scan_scratch_bytes(size_t nentries, size_t nqueries);
+struct SstScanArgs {
+  const uint8_t* keys;
+  const uint64_t* key_off;
+  const uint32_t* key_len;
+  const uint64_t* val_off;
+  const uint32_t* val_len;
+  uint32_t n;
+  uint64_t snapshot;
+  const uint8_t* qkeys;
+  const uint64_t* start_off;
+  const uint32_t* start_len;
+  const uint64_t* limit_off;
+  const uint32_t* limit_len;
+  const uint32_t* q_max;  // may be null
+  uint32_t nq;
+  uint8_t* scratch;  // the caller's, sst_scan_scratch_bytes long
+  uint64_t* out_key_off;
+  uint32_t* out_key_len;
+  uint64_t* out_val_off;
+  uint32_t* out_val_len;
+  uint32_t* out_src;
+  uint64_t max_out;
+  uint32_t* q_first;
+  uint32_t* q_count;
+  uint8_t* q_status;
+  lvkv_sst_scan_report* report;
+};
+hipError_t launch_sst_scan(const SstScanArgs& a, hipStream_t stream);
 
 #ifdef LVKV_PROBE_BUILD
 // Probe builds (tools/probe/liblvkv_probe.so): timestamp buffers and knobs
