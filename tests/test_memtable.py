@@ -160,9 +160,16 @@ def split(rng, n, nb):
     return [b - a for a, b in zip([0] + cuts, cuts + [n])]
 
 
-def random_key(rng):
+# a second alphabet: the bytes a signed compare, a zero-padded prefix and the tile's padding
+# (prefix ~0) get wrong
+WIDE = np.array([0x00, 0x61, 0x7f, 0x80, 0xff], dtype=np.uint8)
+
+
+def random_key(rng, alphabet=None):
     n = int(rng.choice([0, 1, 3, 7, 8, 9, 12, 16, 24, 40]))
-    return rng.integers(97, 100, n, dtype=np.uint8).tobytes()
+    if alphabet is None:
+        return rng.integers(97, 100, n, dtype=np.uint8).tobytes()
+    return alphabet[rng.integers(0, len(alphabet), n)].tobytes()
 
 
 # ---- sizes ----------------------------------------------------------------------------------
@@ -215,6 +222,101 @@ def test_varints_split_across_the_window_edge(lvkv, gpu):
         m = Mem(lvkv, gpu, batch, [0], [len(batch)])
         assert m.buf.data_ptr() % 16 == 0
         assert m.call().check()["nentries"] == nfill + 3
+
+
+# ---- spare capacity, the tile's padding, the other tiles --------------------------------------
+
+def spare_capacity_case(lvkv, gpu, n, max_entries, nb):
+    """n entries over nb batches into max_entries slots: the grids are sized by
+    max_entries, the true count is the control words'. check() holds the order
+    and the fill past nentries."""
+    rng = np.random.default_rng(100000 * nb + 10 * n + max_entries % 7)
+    keys = [random_key(rng, WIDE if i % 2 else None) for i in range(n)]
+    laid = laid_out(batches_of(rng, split(rng, n, nb), lambda i: keys[i], vlen=lambda i: i % 23),
+                    gap=lambda b: b % 3)
+    need = mm.from_batches(*laid)["report"]["key_bytes"]
+    m = Mem(lvkv, gpu, *laid, max_entries=max_entries, key_capacity=need + 300 + n % 9,
+            max_sequence=n // 2, shift=n % 16)
+    rep = m.call().check()
+    assert rep["nentries"] == n and rep["status"] == mm.OK and m.me == max_entries > n
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,max_entries", [(1, 2 * T + 1), (T - 1, T + 1), (T + 1, 4 * T + 3),
+                                           (2 * T + 1, 8 * T)])
+@pytest.mark.parametrize("nb", [1, 9])
+def test_spare_capacity_across_tiles(lvkv, gpu, n, max_entries, nb):
+    spare_capacity_case(lvkv, gpu, n, max_entries, nb)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nb", [1, 9])
+def test_spare_capacity_and_no_entry_at_all(lvkv, gpu, nb):
+    b = [mm.batch(50 + i, 0, b"") for i in range(nb)]
+    m = Mem(lvkv, gpu, *laid_out(b, gap=lambda b: b % 3), max_entries=2 * T, key_capacity=300)
+    rep = m.call().check()
+    assert (rep["status"], rep["nentries"], rep["key_bytes"]) == (mm.OK, 0, 0)
+    assert rep["max_sequence_out"] == 50 + nb - 2  # (sequence + count - 1 of the last batch)
+
+
+# (eight 0xff and a ninth byte of 0xff is the key of nine: 22 keys)
+TIE_KEYS = sorted({b"\xff" * l for l in range(7, 13)} |
+                  {b"\xff" * 8 + bytes([x]) for x in (0, 1, 0x7f, 0x80, 0xfe, 0xff)} |
+                  {b"a" + b"\0" * j for j in range(10)} | {b""})
+
+
+def padding_case(lvkv, gpu, n, tile):
+    """Keys whose prefix word ties with the padding's (eight 0xff bytes and
+    more) or with one another's through the zero padding of a short key, each
+    in three versions: two in the first tile, one in the last; random keys over
+    every byte value around them."""
+    rng = np.random.default_rng(n)
+    step = (tile - 40) // len(TIE_KEYS)
+    assert step >= 2 and n - len(TIE_KEYS) >= tile
+    at = {}
+    for j, k in enumerate(TIE_KEYS):
+        at[3 + step * j] = at[3 + step * j + step // 2] = at[n - 1 - j] = k
+    assert len(at) == 3 * len(TIE_KEYS)
+    full = np.arange(256, dtype=np.uint8)
+    keys = [at[i] if i in at else random_key(rng, full) for i in range(n)]
+    laid = laid_out(batches_of(rng, split(rng, n, 5), lambda i: keys[i], vlen=lambda i: i % 11))
+    m = Mem(lvkv, gpu, *laid)
+    rep = m.call().check()
+    assert rep["nentries"] == n and rep["status"] == mm.OK
+    # the model's order has what the case is for: the 0xff keys last, after every random key
+    ties = [k for k in TIE_KEYS if k[:8] == b"\xff" * 8]
+    assert [k[:-8] for k in m.want["ikeys"][-3 * len(ties):]] == [k for k in ties for _ in range(3)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [T + 37, 2 * T])
+def test_keys_that_tie_with_the_padding_and_with_zero_padded_prefixes(lvkv, gpu, n):
+    """n = T + 37: the second tile is mostly padding; n = 2 T: there is none."""
+    padding_case(lvkv, gpu, n, T)
+
+
+def test_the_debug_tile_is_one_of_three(lvkv):
+    f = lvkv.lib.lvkv_debug_set_memtable_tile
+    try:
+        for bad in (-1, 1, 2, 256, 511, 513, 1023, 1025, 2047, 2049, 4096, 1 << 20, -512):
+            assert f(bad) != 0, bad
+        for good in (512, 1024, 2048, 0):
+            assert f(good) == 0
+    finally:
+        assert f(0) == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tile", [512, 2048])
+def test_the_other_sort_tiles(lvkv, gpu, tile):
+    assert lvkv.lib.lvkv_debug_set_memtable_tile(tile) == 0
+    try:
+        for n in (tile - 1, tile + 1, 2 * tile + 1):
+            spare_capacity_case(lvkv, gpu, n, n + tile + 3, 9)
+        padding_case(lvkv, gpu, tile + 37, tile)
+        padding_case(lvkv, gpu, 2 * tile, tile)
+    finally:
+        assert lvkv.lib.lvkv_debug_set_memtable_tile(0) == 0
 
 
 # ---- keys -----------------------------------------------------------------------------------
@@ -427,9 +529,9 @@ def test_invalid_arguments_and_the_empty_call(lvkv, gpu):
 
 # ---- random cases, and calls back to back ---------------------------------------------------
 
-def random_case(rng):
+def random_case(rng, alphabet=None):
     nb = int(rng.integers(1, 9))
-    keys = [random_key(rng) for _ in range(12)]
+    keys = [random_key(rng, alphabet) for _ in range(12)]
     b = batches_of(rng, [int(rng.integers(0, 30)) for _ in range(nb)],
                    lambda i: keys[int(rng.integers(0, len(keys)))], seq0=int(rng.integers(0, 1 << 40)),
                    vlen=lambda i: int(rng.integers(0, 50)))
@@ -446,8 +548,17 @@ def random_case(rng):
 
 @pytest.mark.gpu
 def test_random_cases_on_one_set_of_dirty_buffers(lvkv, gpu):
+    random_cases(lvkv, gpu, 2024, None)
+
+
+@pytest.mark.gpu
+def test_random_cases_over_the_wide_alphabet(lvkv, gpu):
+    random_cases(lvkv, gpu, 2026, WIDE)
+
+
+def random_cases(lvkv, gpu, seed, alphabet):
     import torch
-    rng = np.random.default_rng(2024)
+    rng = np.random.default_rng(seed)
     cap, kcap, nbmax = 512, 1 << 16, 8
     scratch = torch.full((int(lvkv.lib.lvkv_memtable_scratch_bytes(nbmax, cap)),), FILL,
                          dtype=torch.uint8, device=gpu)
@@ -460,7 +571,7 @@ def test_random_cases_on_one_set_of_dirty_buffers(lvkv, gpu):
     rep = torch.zeros(ctypes.sizeof(lvkv.MemtableReport), dtype=torch.uint8, device=gpu)
     seen = set()
     for case in range(200):
-        payload, offs, lens = random_case(rng)
+        payload, offs, lens = random_case(rng, alphabet)
         paranoid = bool(case % 3 == 0)
         want = mm.from_batches(payload, offs, lens, max_sequence=case, paranoid=paranoid,
                                max_entries=cap, key_capacity=kcap)

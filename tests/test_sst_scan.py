@@ -22,6 +22,7 @@ import pytest
 
 import memtable_model as memm
 import scan_model as sm
+import store_model as st
 import vtable_model as vm
 from conftest import GOLDEN, REPO
 from test_memtable import batches_of, laid_out
@@ -265,12 +266,41 @@ def test_none_eligible_and_all_visible(lvkv, gpu):
 
 # ---- key shapes -------------------------------------------------------------------------
 
+# a second alphabet for the seeded user keys: the bytes a signed compare and a compare that
+# stops at a zero byte get wrong
+WIDE = np.array([0x00, 0x61, 0x7f, 0x80, 0xff], dtype=np.uint8)
+
+
+def draw(rng, n, alphabet, lo, hi):
+    """n bytes of the alphabet, or -- none given -- of lo .. hi - 1 (the
+    draws the seeded cases have always made)."""
+    if alphabet is None:
+        return rng.integers(lo, hi, n, dtype=np.uint8).tobytes()
+    return alphabet[rng.integers(0, len(alphabet), n)].tobytes()
+
+
+def with_prefixes(users):
+    """The keys and the first half of each: keys that are prefixes of others."""
+    return sorted(set(users) | {u[:len(u) // 2] for u in users})
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("aligned,gap", [(True, 0), (False, 0), (False, 1), (False, 3), (False, 7)])
 def test_keys_at_odd_and_aligned_offsets(lvkv, gpu, aligned, gap):
+    offsets_case(lvkv, gpu, aligned, gap, None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("aligned,gap", [(True, 0), (False, 0), (False, 3)])
+def test_wide_alphabet_keys_at_odd_and_aligned_offsets(lvkv, gpu, aligned, gap):
+    offsets_case(lvkv, gpu, aligned, gap, WIDE)
+
+
+def offsets_case(lvkv, gpu, aligned, gap, alphabet):
     rng = np.random.default_rng(gap + 10 * aligned)
-    users = sorted({rng.integers(97, 100, int(rng.integers(0, 20)), dtype=np.uint8).tobytes()
-                    for _ in range(120)})
+    users = sorted({draw(rng, int(rng.integers(0, 20)), alphabet, 97, 100) for _ in range(120)})
+    if alphabet is not None:
+        users = with_prefixes(users)
     entries = []
     for i, u in enumerate(users):
         entries += [(ikey(u, s, t), 4) for s, t in ((90, 1), (60, i % 3 and 1), (30, 1))][:1 + i % 3]
@@ -298,6 +328,58 @@ def test_long_keys_that_differ_in_their_last_byte(lvkv, gpu, klen, aligned):
     assert [c for _, c, _ in per_query] == [2, 3, 1, 0, 1, 0, 0]
     assert len(src) == 20  # (the versions at 40: values for odd b)
     Call(buf, entries, 35, queries, aligned=aligned, gap=0 if aligned else 5).check()
+
+
+# ---- the store's special keys ---------------------------------------------------------------
+
+def near_misses(k):
+    out = [k + b"\x00"]
+    if k:
+        out.append(k[:-1])
+        if k[-1]:
+            out.append(k[:-1] + bytes([k[-1] - 1]))
+    return out
+
+
+def special_case(seam, which):
+    """Every key of store_model.SPECIAL in several versions (a deletion every
+    fourth), the versions of `which` lying around position `seam`. Returns
+    (entries, queries, snapshots)."""
+    users = sorted(st.SPECIAL)
+    before = users[:users.index(which)]
+    nv = {u: 5 for u in users}
+    nv[which] = 9
+    fill = seam - nv[which] // 2 - 5 * len(before)
+    assert before and fill >= 0
+    for j, u in enumerate(before):
+        nv[u] += fill // len(before) + (j < fill % len(before))
+    entries = [(ikey(u, 9000 - 3 * v, 0 if v % 4 == 3 else 1), 1 + v % 7)
+               for u in users for v in range(nv[u])]
+    keys = [k for k, _ in entries]
+    assert keys[seam - 1][:-8] == keys[seam][:-8] == which
+    pool = sorted(set(users) | {m for u in users for m in near_misses(u)})
+    queries = [(p, None, 2) for p in pool] + [(p, q, None) for p, q in zip(pool, pool[1:])] + \
+        [(which, None, None), (b"", which, None), (which, which[:-1], None)]
+    # (readers that see version 0, 2, 6 and 8 first: values, the last two of the longer keys)
+    return entries, queries, (sm.MAX_SEQUENCE, 9000 - 3 * 2, 9000 - 3 * 5 - 1, 9000 - 3 * 8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", [b"a\x00", st.PAIRS[1], b"\xff" * 8],
+                         ids=["zero_padded", "pair_at_8", "eight_ff"])
+@pytest.mark.parametrize("seam", ["group", "tile"])
+def test_order_of_the_special_keys_across_a_seam(lvkv, gpu, seam, which):
+    """Order decided past a shared prefix, by a zero byte, by 0x7f against
+    0x80 and among 0xff bytes, with one key's versions across a workgroup's
+    end or the scan tile's; starts and limits on the keys and on their near
+    misses."""
+    entries, queries, snapshots = special_case(GROUP if seam == "group" else TILE, which)
+    buf = _fresh(lvkv, gpu, len(entries), len(queries))
+    for k, snapshot in enumerate(snapshots):
+        src, per_query, rep = Call(buf, entries, snapshot, queries, aligned=k == 1,
+                                   gap=(1, 0, 3, 7)[k]).check()
+        assert rep["num_visible"] and rep["num_hidden"]
+    assert rep["num_above_snapshot"] and rep["num_deletions"]
 
 
 # ---- queries ----------------------------------------------------------------------------------
@@ -376,10 +458,11 @@ def test_capacity_one_short_then_the_repeat(lvkv, gpu):
 
 # ---- seeded cases, reuse -----------------------------------------------------------------------
 
-def random_case(rng):
+def random_case(rng, alphabet=None):
     nusers = int(rng.integers(1, 14))
-    users = sorted({rng.integers(97, 99, int(rng.integers(0, 5)), dtype=np.uint8).tobytes()
-                    for _ in range(nusers)})
+    users = sorted({draw(rng, int(rng.integers(0, 5)), alphabet, 97, 99) for _ in range(nusers)})
+    if alphabet is not None:
+        users = with_prefixes(users)
     entries = []
     for u in users:
         tags = sorted({(int(rng.integers(0, 12)) << 8) | int(rng.choice([0, 1, 1, 1, 2]))
@@ -398,11 +481,20 @@ def random_case(rng):
 
 @pytest.mark.gpu
 def test_random_cases_on_one_set_of_dirty_buffers(lvkv, gpu):
-    rng = np.random.default_rng(2025)
+    random_cases(lvkv, gpu, 2025, None)
+
+
+@pytest.mark.gpu
+def test_random_cases_over_the_wide_alphabet(lvkv, gpu):
+    random_cases(lvkv, gpu, 2027, WIDE)
+
+
+def random_cases(lvkv, gpu, seed, alphabet):
+    rng = np.random.default_rng(seed)
     buf = _fresh(lvkv, gpu, 200)
     seen = set()
     for i in range(300):
-        entries, snapshot, queries = random_case(rng)
+        entries, snapshot, queries = random_case(rng, alphabet)
         max_out = None if i % 9 else int(rng.integers(0, 4))
         _, per_query, rep = Call(buf, entries, snapshot, queries, max_out=max_out,
                                  aligned=i % 4 == 0, gap=i % 3).check()
